@@ -9,6 +9,12 @@ is functional (reads the committed state, writes outputs and the next state
 to separate buffers), so K steps recompute the same tick without cached work.
 
 Prints one JSON line (rank 0).  Multi-GPU: see DESIGN.md §6.
+
+A plain run sets up, warms up, times the K steps, measures the commit's share of a
+step (committed_tick: the headline is the committed tick) and prints the line.
+--full adds what takes runs of its own: per-kernel device times and the roofline,
+the CPU baseline, the host-observed rate, the stream workload's PCIe-inclusive pass.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -77,6 +83,32 @@ def emit_shard_bytes(Q, own_q, F_local, O_local, n_local, Qn_out):
     global sequence, 8 B), own c_arr read + free_processes write (8 B per own
     queued worker), log shard re-read for orphan compaction and orphan ids."""
     return 9 * Q + 4 * Qn_out + 8 * n_local + 8 * own_q + 4 * F_local + 8 * O_local
+
+
+DUMP_MAX_ELEMS = 1 << 20  # per array; larger outputs are sampled (fixed seed), 8 MB each as float64
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float64 (every value here is an
+    integer below 2**53, so exact).  An array of more than DUMP_MAX_ELEMS entries is
+    written as a sample at sorted indices drawn with a fixed seed, the same for every run
+    of the same length.  An empty array gets no file."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size == 0:  # nothing to compare (the result record holds the count)
+            continue
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
+def result_row(r):
+    """What a TickResult dict says about the tick's results, as a row of numbers (not
+    `reruns`: how the library got there, not what it computed)."""
+    return [r[k] for k in ("n_assigned", "n_orphans", "queue_len", "log_head", "n_evicted", "fill_level",
+                           "max_free")]
 
 
 def cpu_baseline(st, T, budget_s=10.0):
@@ -211,7 +243,7 @@ def bench_stream(args, dist=None, world=1, rank=0, dev=0):
             torch.cuda.synchronize()
             stage(ticks[0])
 
-        if mode == "hbm" and not args.no_pcie_pass:
+        if args.full and mode == "hbm" and not args.no_pcie_pass:
             # the PCIe-inclusive rate (pinned host batches copied inside the timed region),
             # measured first on the same ticks from the same initial state: reported beside
             # the value, never as it
@@ -283,13 +315,13 @@ def bench_stream(args, dist=None, world=1, rank=0, dev=0):
         dist.all_reduce(t[:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:])
         dt, stats["evicted"] = float(t[0].item()), int(t[1].item())
-    g.timing_enable(True)
-    loop(Wu + K, len(ticks))
-    kt = g.timing_read()
-    g.timing_enable(False)
-    wstats = g.window_stats() if world == 1 else (0, 0)
-    kern = {k: ms / max(n, 1) * 1e3 for k, (ms, n) in kt.items()}  # us per launch
-    per_tick = {k: ms / K * 1e3 for k, (ms, n) in kt.items()}      # us per tick
+    if args.dump_outputs:
+        # what the K timed ticks returned, and the committed state they left behind (its log
+        # holds every tick's assignments in order)
+        state = g.read_state()
+        dump_outputs(args.dump_outputs, dict(results=np.array([result_row(r) for r in rs], np.float64),
+                                             **{"state_" + k: state[k] for k in ("reg", "free", "hb", "epoch",
+                                                                                 "queue", "log")}))
     line = {
         "metric": "streaming task assignments/sec, configs[4] (64K tasks + churn per tick, 1M workers)",
         "value": stats["assigned"] / dt,
@@ -316,9 +348,31 @@ def bench_stream(args, dist=None, world=1, rank=0, dev=0):
                                   "pageable": "pageable (staged by copy)"}[mode],
                    "orphans_per_tick": stats["orphans"] / K, "evicted_per_tick": stats["evicted"] / K,
                    "parallelism": "dp1" if world == 1 else "worker-table shards x%d" % world},
-        "tick": {"device_us_per_tick": sum(per_tick.values()), "kernels_us_per_tick": per_tick,
-                 "kernels_us_per_launch": kern},
+        "tick": {},
     }
+    if args.full:
+        stream_full(args, g, loop, ticks, line, stats, pcie, W, T, K, Wu, world, dt, B_ticks)
+    if world == 1:
+        # window ticks (DESIGN.md §5b) among all the ticks this process ran, and fallbacks
+        line["tick"]["window_ticks"], line["tick"]["window_fallbacks"] = g.window_stats()
+    if dist is not None:
+        line["config"]["world_size_reported"] = dist.get_world_size()
+        line["config"]["backend"] = dist.get_backend()
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+
+
+def stream_full(args, g, loop, ticks, line, stats, pcie, W, T, K, Wu, world, dt, B_ticks):
+    """--full, stream workload: K more ticks under per-kernel timing, the roofline of the
+    dominant kernel, and the PCIe-inclusive pass measured before the timed region."""
+    g.timing_enable(True)
+    loop(Wu + K, len(ticks))
+    kt = g.timing_read()
+    g.timing_enable(False)
+    kern = {k: ms / max(n, 1) * 1e3 for k, (ms, n) in kt.items()}  # us per launch
+    per_tick = {k: ms / K * 1e3 for k, (ms, n) in kt.items()}      # us per tick
+    line["tick"] = {"device_us_per_tick": sum(per_tick.values()), "kernels_us_per_tick": per_tick,
+                    "kernels_us_per_launch": kern}
     # roofline: the dominant kernel's share of SURVEY.md 8(d)'s tick bytes (one GPU: the apply
     # launch carries the slot purge, 24 B per worker, and the messages, 17 B each) over its
     # event-timed launch average; tick_frac: the whole tick's 8(d) bytes on the driver's clock
@@ -350,14 +404,6 @@ def bench_stream(args, dist=None, world=1, rank=0, dev=0):
                         "tick_frac": B_ticks / dt / 1e9 / HBM_PEAK_GBS}
     if pcie is not None:
         line["pcie_inclusive"] = pcie
-    if world == 1:
-        # window ticks (DESIGN.md §5b) among all the ticks this process ran, and fallbacks
-        line["tick"]["window_ticks"], line["tick"]["window_fallbacks"] = wstats
-    if dist is not None:
-        line["config"]["world_size_reported"] = dist.get_world_size()
-        line["config"]["backend"] = dist.get_backend()
-    if rank == 0:
-        print(json.dumps(line), flush=True)
 
 
 # The reference loop itself (task_dispatcher.py:324-419, CPython, one core), measured
@@ -543,7 +589,16 @@ def main():
     ap.add_argument("--loads", default="zipf", choices=("zipf", "uniform"),
                     help="uniform: BASELINE configs[1]'s state (capacity 256, busy ~U[0,128); "
                          "use with --workers 1000 --tasks 100000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel device times and the roofline (a gated pass of "
+                         "their own), the one-core CPU baseline, the host-observed rate (readback + commit), the "
+                         "exchange's own time (N GPUs), the stream workload's PCIe-inclusive pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (tick workloads: its "
+                         "result record, assignments, orphans and evicted slots, an empty list left out; stream: "
+                         "every timed tick's result record and the committed state) as DIR/<name>.npy, float64; "
+                         "arrays of more than 1M entries as a fixed seeded sample.  One GPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-host-observed", action="store_true", help="skip the launch+wait+readback+commit timing")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
@@ -569,6 +624,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes the one-GPU outputs (--gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     if args.workload == "stream" and args.gpus == 1:
@@ -688,6 +747,25 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        # the last timed step: its result record and the lists a caller reads after wait()
+        last = g.wait()
+        dump_outputs(args.dump_outputs, dict(result=np.array(result_row(last), np.float64), assign=g.assignments(),
+                                             orphans=g.orphans(), evicted=g.evicted()))
+    B = tick_bytes(W, Q, F, O, n_assigned)
+    kern = None
+    if args.full:
+        kern = tick_kernels(args, g, step, dist, barrier, world, deque, W, T, Q, F, O, n_assigned, res, B)
+    tick_report(args, g, dist, rank, world, deque, st, W, T, Q, F, O, n_assigned, n_evicted, res, dt, t_enq, B, kern)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def tick_kernels(args, g, step, dist, barrier, world, deque, W, T, Q, F, O, n_assigned, res, B):
+    """--full, tick workloads: the steps again under per-kernel timing, the dominant
+    kernel's roofline figures, and (N GPUs) the exchange all-reduce timed alone."""
+    if world > 1:
+        import torch
     # per-kernel device time with HIP packet events on the balancer's stream (same K): one
     # GPU, the K steps gated (run back to back on the device, gated_timing); sharded, the
     # exchange between the phases syncs with the host (gloo), so those launches are not gated
@@ -716,7 +794,6 @@ def main():
             ev1.record(g.stream)
         ev1.synchronize()
         kern["exchange_allreduce"] = (ev0.elapsed_time(ev1) / args.steps, args.steps)
-        kt_x_bytes = xb.numel()
 
     # fused one-GPU heartbeat ticks (scan + emit only, W <= 128K slots): the emit's log
     # workgroups read the in-flight log and flag the orphans, k_scan has no log role
@@ -738,7 +815,6 @@ def main():
         dom_bytes = logscan_bytes(W, F)
     else:
         dom_bytes = tick_bytes(W // world, Q, F // world, O // world, n_assigned // world)
-    B = tick_bytes(W, Q, F, O, n_assigned)
     # roofline bytes: SURVEY.md §8(d) -- the dominant kernel's share of the tick's bytes
     # (one-GPU configs[2]: the emit carries everything but k_scan's 16 B per worker read);
     # the builder's per-kernel model (queue / record traffic §8(d) does not count) beside it
@@ -750,7 +826,6 @@ def main():
     else:
         bytes_model = "builder model (bench.py: %s_bytes)" % dom
     achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    value = n_assigned * args.steps / dt  # whole job: the global tick's dispatches
     # HBM bytes per launch of the dominant kernel from the committed PMC passes of
     # this same command (tools_profile.sh -> tools/prof_summary.py), when they match
     traffic, traffic_src, rocprof_ms = None, None, None
@@ -768,6 +843,28 @@ def main():
                            "so for this kernel's 4-8 B gathers the figure is an upper bound), rocprof average over the "
                            "gated timing pass from profiles/%s_kernel_timed.csv (all launches: %s_kernel_stats.csv); "
                            "summary profiles/%s_traffic.json" % (tj["tag"], tj["tag"], tj["tag"], tj["tag"]))
+    return {
+        "tick_dev_ms": tick_dev_ms, "gate_timed_out": gate_timed_out,
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                     "algorithmic_bytes": dom_bytes, "bytes_model": bytes_model,
+                     "kernel_avg_ms": dom_ms, "kernel_avg_ms_rocprof": rocprof_ms,
+                     "frac_rocprof": (dom_bytes / (rocprof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if rocprof_ms else None,
+                     "model_frac": model_frac},
+        "tick": {"algorithmic_bytes": B, "device_ms": tick_dev_ms,
+                 "achieved_GBs": B / (tick_dev_ms * 1e-3) / 1e9,
+                 "kernels_avg_ms": {k: v[0] for k, v in kern.items()},
+                 "kernel_timing": ("packet events of the K steps relaunched behind a timing gate (back to back on the "
+                                   "device, bench.py: gated_timing)" if world == 1 else
+                                   "packet events of K host-paced steps (the exchange syncs with the host)"),
+                 "gate_timed_out": gate_timed_out},
+    }
+
+
+def tick_report(args, g, dist, rank, world, deque, st, W, T, Q, F, O, n_assigned, n_evicted, res, dt, t_enq, B, kern):
+    """The result line of a tick workload.  `kern`: tick_kernels' figures (--full) or None."""
+    value = n_assigned * args.steps / dt  # whole job: the global tick's dispatches
+    kt_x_bytes = g.exchange().numel() if world > 1 else 0
     line = {
         "metric": "task assignments/sec + % HBM roofline, 1M tasks x 64K workers, 1/2/4/8 GPU",
         "value": value,
@@ -803,30 +900,25 @@ def main():
                    "assigned_per_tick": n_assigned, "evicted": n_evicted,
                    "fill_level": int(res["fill_level"]),
                    "parallelism": "dp1" if world == 1 else "worker-table shards x%d" % world},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes": dom_bytes, "bytes_model": bytes_model,
-                     "kernel_avg_ms": dom_ms, "kernel_avg_ms_rocprof": rocprof_ms,
-                     "frac_rocprof": (dom_bytes / (rocprof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if rocprof_ms else None,
-                     "model_frac": model_frac,
-                     # the whole tick on the driver's clock: SURVEY.md 8(d) tick bytes / ms_per_step
+        # the whole tick on the driver's clock: SURVEY.md 8(d) tick bytes / ms_per_step (the
+        # per-kernel figures beside it come with --full)
+        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "tick_frac": B / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
-        "tick": {"algorithmic_bytes": B, "device_ms": tick_dev_ms,
-                 "achieved_GBs": B / (tick_dev_ms * 1e-3) / 1e9,
-                 "kernels_avg_ms": {k: v[0] for k, v in kern.items()},
-                 "kernel_timing": ("packet events of the K steps relaunched behind a timing gate (back to back on the "
-                                   "device, bench.py: gated_timing)" if world == 1 else
-                                   "packet events of K host-paced steps (the exchange syncs with the host)"),
-                 "gate_timed_out": gate_timed_out},
+        "tick": {"algorithmic_bytes": B},
     }
-    # the per-kernel times must fit in the step they were measured for: their sum per step
-    # against the timed region's ms_per_step.  (The gated span itself is not a step time: the
-    # packet events add ~8 us between launches, profiles/r06b_trace_gaps.txt.)
-    lim = dt * 1e3 / args.steps * 1.05
-    line["tick"]["kernels_fit_step"] = bool(tick_dev_ms <= lim) and not gate_timed_out
-    if not line["tick"]["kernels_fit_step"]:
-        line["roofline"]["flag"] = ("per-kernel times (sum %.4f ms) exceed the step (%.4f ms x 1.05) or the gate timed "
-                                    "out: roofline.frac is not a kernel property on this run" % (tick_dev_ms, lim / 1.05))
+    if kern is not None:
+        line["roofline"].update(kern["roofline"])
+        line["tick"] = kern["tick"]
+        tick_dev_ms, gate_timed_out = kern["tick_dev_ms"], kern["gate_timed_out"]
+        # the per-kernel times must fit in the step they were measured for: their sum per step
+        # against the timed region's ms_per_step.  (The gated span itself is not a step time: the
+        # packet events add ~8 us between launches, profiles/r06b_trace_gaps.txt.)
+        lim = dt * 1e3 / args.steps * 1.05
+        line["tick"]["kernels_fit_step"] = bool(tick_dev_ms <= lim) and not gate_timed_out
+        if not line["tick"]["kernels_fit_step"]:
+            line["roofline"]["flag"] = ("per-kernel times (sum %.4f ms) exceed the step (%.4f ms x 1.05) or the gate "
+                                        "timed out: roofline.frac is not a kernel property on this run"
+                                        % (tick_dev_ms, lim / 1.05))
     if deque:
         line["metric"] = "task assignments/sec, start() loop (no heartbeats), 1M tasks x 64K workers"
         line["data"] = "synthetic (faasbal.synth.zipf_deque_state, seed=0, dup_frac=0.02)"
@@ -835,14 +927,15 @@ def main():
         line["config"]["backend"] = dist.get_backend()
     if args.workload == "cfg3":
         line["metric"] = "task assignments/sec, 16M tasks x 1M workers, 1/2/4/8 GPU"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_deque(st, T, args.cpu_budget) if deque else \
             cpu_baseline(st, T, args.cpu_budget)
         if not deque:
             line["reference_python_value"] = REFERENCE_PYTHON
     if world == 1 and not deque:
         cm = committed_tick(st, T)
-        cm["device_ms_with_commit"] = tick_dev_ms + cm["commit_in_tick_ms"]
+        if kern is not None:
+            cm["device_ms_with_commit"] = kern["tick_dev_ms"] + cm["commit_in_tick_ms"]
         cm["ms_per_step_with_commit"] = dt * 1e3 / args.steps + cm["commit_in_tick_ms"]
         cm["value_with_commit"] = n_assigned / (cm["ms_per_step_with_commit"] * 1e-3)
         # the headline is the committed tick: value / ms_per_step carry the commit's device cost
@@ -861,12 +954,10 @@ def main():
                       "ms_per_step_with_commit = the timed region's ms_per_step + that delta (the line's value and "
                       "ms_per_step)" % (n_evicted, O))
         line["committed"] = cm
-    if world == 1 and not args.no_host_observed:
+    if args.full and world == 1 and not args.no_host_observed:
         line["host_observed"] = host_observed(g, st, T, min(args.steps, 50), n_assigned)
     if rank == 0:
         print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

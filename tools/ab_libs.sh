@@ -2,13 +2,13 @@
 # A/B of kernel variant libraries (distributed-faas_amd/faasbal/ab/libfaasbal_<V>.so) on
 # the stream bench (AB_WORKLOAD: another workload), alternated twice: tools/ab_libs.sh TAG V1 V2 ...
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
+R=$(pwd); mkdir -p bench_out
 TAG=$1; shift
 for rep in 1 2; do
   for V in "$@"; do
-    FAASBAL_LIB=$R/distributed-faas_amd/faasbal/ab/libfaasbal_$V.so timeout -k 10 200 python -u bench.py --workload ${AB_WORKLOAD:-stream} \
-        --no-cpu-baseline --no-pcie-pass --no-host-observed --steps ${AB_STEPS:-30} > gpurun_out/${TAG}_$V$rep.json 2> gpurun_out/${TAG}_$V$rep.err || { tail -5 gpurun_out/${TAG}_$V$rep.err; exit 1; }
-    python3 - gpurun_out/${TAG}_$V$rep.json $V <<'PY'
+    FAASBAL_LIB=$R/distributed-faas_amd/faasbal/ab/libfaasbal_$V.so timeout -k 10 200 python -u bench.py --full --workload ${AB_WORKLOAD:-stream} \
+        --no-cpu-baseline --no-pcie-pass --no-host-observed --steps ${AB_STEPS:-30} > bench_out/${TAG}_$V$rep.json 2> bench_out/${TAG}_$V$rep.err || { tail -5 bench_out/${TAG}_$V$rep.err; exit 1; }
+    python3 - bench_out/${TAG}_$V$rep.json $V <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 t = d["tick"]

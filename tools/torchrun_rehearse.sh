@@ -4,10 +4,10 @@
 # with RCCL on an 8-GPU node.
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-cd $R && mkdir -p gpurun_out
+cd $R && mkdir -p bench_out
 for N in ${NS:-2 4}; do
   timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-      --master-port $((29500 + N)) bench.py --gpus $N --steps ${STEPS:-50} --warmup 5 --backend gloo \
-      > gpurun_out/tr_n$N.json 2> gpurun_out/tr_n$N.err || { tail -30 gpurun_out/tr_n$N.err; exit 1; }
-  cat gpurun_out/tr_n$N.json
+      --master-port $((29500 + N)) bench.py --full --gpus $N --steps ${STEPS:-50} --warmup 5 --backend gloo \
+      > bench_out/tr_n$N.json 2> bench_out/tr_n$N.err || { tail -30 bench_out/tr_n$N.err; exit 1; }
+  cat bench_out/tr_n$N.json
 done
