@@ -20,6 +20,7 @@
 
 #include "faasbal.h"
 #include "faasbal_kernels.h"
+#include "faasbal_plan.h"
 
 using namespace fb;
 
@@ -190,7 +191,6 @@ struct fb_ctx {
     unsigned long long *ev_head = nullptr;  // per slot {link stamp, last linked message}
     int32_t *ev_next = nullptr;             // per message
     uint32_t link = 0;                      // stamp of the last k_ev_link launch
-    int ev_ll = 1;                          // fb_set_path("ev_ll", 0): always the radix sort (test paths)
     bool l_resort = false;                  // this tick reruns through the sort (a slot had > kLinkMax messages)
     bool l_used_ll = false;                 // the last enqueue grouped by linked lists
     void *h_stage = nullptr;  // two pinned halves of E_cap events each (fb_tick_stage)
@@ -240,17 +240,9 @@ struct fb_ctx {
     HostOut *hout = nullptr, *hout_dev = nullptr;  // host-mapped results written by k_emit
     unsigned long long *dbg = nullptr;             // diagnostic stamps
     size_t dbg_n = 0;
-    // fb_set_path: the launch sequences of other table sizes on small (oracle-checkable)
-    // inputs (test paths)
-    int force_plan = 0;    // "plan": 1 the k_plan2 + k_emit2 path, 2 the chunked k_emit (R > 128)
-    int rs_wide = 1;       // "rs_wide": 0 8-bit sort digits only (the path past kRsWideMaxBlocks tiles)
-    int logscan = -1;      // "logscan": -1 auto (k_logscan for large tables when the bitmap fits in LDS)
+    PathKnobs paths;       // fb_set_path (faasbal_plan.h)
     int ncu = 0, max_lds = 0;
     int win_occ = 0;       // k_emit_win workgroups resident per CU (occupancy calculator)
-    int split_slots = -1;  // "split_slots": -1 auto (separate k_slots launch once the records outgrow L2)
-    // "fault_qlen": the next fb_tick_wait overwrites the device-reported queue length with this
-    // value before validating it (tests of check_lengths; -1 = off)
-    int64_t fault_qlen = -1;
     // deque contexts (fb_create_deque): PushDispatcher.start, task_dispatcher.py:251-322
     int deque = 0;
     int32_t *tokcnt[2] = {nullptr, nullptr}, *xw[2] = {nullptr, nullptr}, *kl[2] = {nullptr, nullptr};
@@ -295,18 +287,7 @@ struct fb_ctx {
     uint32_t *ocnt = nullptr, *osegcnt = nullptr;
     uint32_t *xg_acc = nullptr, *xg_tk = nullptr, *ogrp = nullptr;  // exchanged group rows (phase 1 -> 2)
     uint32_t *xs_tk = nullptr;                        // k_xscan's ticket
-    int gp_on = 1;                                    // fb_set_path("gp", 0): large one-GPU tables run k_plan2
-    int win_direct = 1;                               // fb_set_path("win_direct", 0): k_emit_win chunks by ticket
-    int xself_on = 1;                                 // fb_set_path("xself", 0): k_xscan's last workgroup prefixes the chunks
-    int wfirst_on = 1;                                // fb_set_path("wfirst", 0): phase-1 k_scan queue blocks first
-    int gpcheck = 0;                                  // fb_set_path("gpcheck", 1): diagnostic (stamps builds)
-    int cmix_on = 1;                                  // fb_set_path("cmix"): k_emit2 role interleave
-    int wtiles = 0;                                   // fb_set_path("wtiles"): slot tiles per k_scan W workgroup (0 auto)
-    int qtiles = 0;                                   // fb_set_path("qtiles"): 1 = one queue block per k_scan Q workgroup (0 auto: 4)
-    int lazy_on = 1;                                  // fb_set_path("lazy", 0): commits clear their orphaned log entries
     bool stale_any = false;                           // lazy clears: entries of dead registrations may be in the log
-    int xcfirst_on = 1;                               // fb_set_path("xcfirst", 0): k_emit_shard_xp's compaction workgroups last
-    int xplan_on = 1;                                 // fb_set_path("xplan", 0): large queues take the phase-2 k_scan path
     int full_assign = 0;                              // fb_set_full_assign: phase 2 writes the whole task -> slot array
     bool l_full = false;                              // ... and the last launch did
     int32_t *assign_all = nullptr;                    // (its own allocation, grown as ticks need)
@@ -344,7 +325,6 @@ int fail(fb_ctx *c, int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                                      \
     } while (0)
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 template <typename T>
@@ -499,60 +479,6 @@ int ensure_table(fb_ctx *c, int R, int nbq) {
     return FB_OK;
 }
 
-// Exchange buffer of a sharded tick, summed by one uint8 all-reduce: every byte
-// has at most one nonzero contributor (the owner of the slot, event or position),
-// so the SUM is exact -- except the block rows, whose bytes are 4-bit digits that at
-// most kXRowsMaxWorld ranks add (<= 240).  [rec, c8) -- two copies of the per-rank
-// records (by launch parity), the event regions -- is zero before phase 1 (a memset, or
-// for an idle tick the previous phase 2's zeroing of this parity's records); c8 and the
-// rows are written in full.
-struct XLayout {
-    size_t rec, front, back, evs, c8, rows, grows, total;
-};
-// The phase-2 form of a sharded tick of this shape: 0 phase 2 re-counts the exchanged c
-// values (k_scan) -- > 16 ranks or a table wider than kRFused rows; 1 phase 1 exchanges
-// its per-block round counts as digit rows, a one-launch phase 2 sums them (<= kXRowsMaxBlocks
-// queue blocks); 2 (xplan; larger queues, R = kXGroupR, configs[3]: 3.5 K blocks) the same
-// digit rows, whose per-block prefixes k_xscan scans before k_emit_shard
-inline int xrows_mode(int world, int R, int64_t Qlog) {
-    const int64_t nbq = std::max<int64_t>(1, cdiv(Qlog, kBS));
-    if (world > kXRowsMaxWorld || world * kXRecLines > kBS || R > kRFused) return 0;
-    // (the one-launch phase 2 walks the digit rows and this rank's rows in the same rounds:
-    // their parts per column must agree, as they do for the 32 / 64 / 128-row tables)
-    if (nbq <= kXRowsMaxBlocks && xr_parts(R) == kBS / (R / 4)) return 1;
-    return (nbq > kXRowsMaxBlocks && R == kXGroupR) ? 2 : 0;  // (k_xscan decodes 32-round rows)
-}
-inline size_t xrows_bytes(int world, int R, int64_t Qlog) {
-    const int64_t nbq = std::max<int64_t>(1, cdiv(Qlog, kBS));
-    return xrows_mode(world, R, Qlog) ? (size_t)nbq * xr_row(R) : 0;
-}
-// ... and the group rows (one-launch form, R = kXGroupR only)
-inline size_t xgrows_bytes(int world, int R, int64_t Qlog) {
-    if (R != kXGroupR || xrows_mode(world, R, Qlog) != 1) return 0;
-    const int64_t nbq = std::max<int64_t>(1, cdiv(Qlog, kBS));
-    return (size_t)cdiv(nbq, kXGroupBlocks) * xg_row(R);
-}
-// xcw: bytes per exchanged c (1 while the round table has <= kRFused rows, else 2)
-XLayout xlayout(int world, int64_t E, int64_t Qlog, int xcw = 1, size_t rows = 0, size_t grows = 0) {
-    XLayout x;
-    x.rec = 0;
-    x.front = (size_t)2 * 8 * kXRecWords * world;
-    x.back = x.front + 4 * (size_t)E;
-    x.evs = x.back + 4 * (size_t)E;
-    x.c8 = (x.evs + (size_t)E + 1) & ~(size_t)1;  // 2-byte aligned for the wide form
-    x.rows = (x.c8 + (size_t)xcw * (size_t)Qlog + 15) & ~(size_t)15;
-    x.grows = (x.rows + rows + 15) & ~(size_t)15;
-    x.total = (x.grows + grows + 15) & ~(size_t)15;
-    return x;
-}
-inline int xc_width(int R) { return R > kRFused ? 2 : 1; }
-
-int choose_R(int32_t maxc) {
-    int R = 32;
-    while (R < maxc) R <<= 1;
-    return R;
-}
-
 // The committed window [qoff, qoff + Qn) without its tombstones: slots, free counts and
 // (h non-null) heartbeats on the host.  The stream must be idle.
 int win_read(fb_ctx *c, std::vector<int32_t> &q, std::vector<int32_t> &f, std::vector<double> *h, int64_t &n) {
@@ -689,7 +615,7 @@ int flush_commit(fb_ctx *c) {
 // not older than s's registration (epoch), which every kernel that reads the log tests once
 // such entries may exist (live_chk).  (configs[3]: the fold's ~380 K scattered clears cost
 // 2.9 µs of the committed tick; configs[2]'s 24.6 K, ~0.5 µs.)
-bool lazy_ctx(const fb_ctx *c) { return c->lazy_on && !c->shard && !c->deque; }
+bool lazy_ctx(const fb_ctx *c) { return c->paths.lazy_on && !c->shard && !c->deque; }
 
 // Before a state read hands out the log: the deferred clears, all at once (k_log_normalize),
 // after the last commit.
@@ -704,78 +630,180 @@ int log_settle(fb_ctx *c) {
     return FB_OK;
 }
 
-// Whether the tick about to launch runs as a window tick, and how much of
-// the window it scans: the tasks (T plus about the last tick's orphans), the positions
-// between them that are no longer live, a slack that grows whenever a window tick missed
-// its first unserved element.  Only level-0 ticks qualify (the last tick was one), with
-// messages (the purge rides in k_ev_apply_ll's launch), on the linked-list path.
+// Whether the tick about to launch (c->l_*) runs as a window tick: plan_window's rules on
+// this context's state; c->l_nchW, the window chunks it scans.
 bool win_plan(fb_ctx *c) {
-    const int mode = c->win;
-    if (!c->win_cap || mode == 0 || c->l_E <= 0 || !c->ev_head || !c->ev_ll || c->compact ||
-        c->l_purge_only || c->deque || c->shard)
-        return false;
-    if (mode < 0 && c->last_L != 0) return false;  // auto: after a level-0 tick
-    if (mode > 0 && c->last_L > 0) return false;
-    const int64_t want = (c->l_T + 2 * c->last_O + 256) * 5 / 4 + c->win_slack;
-    const int64_t scan = std::min<int64_t>(c->Qn, want);
-    if (mode < 0 && scan * 2 > c->Qn) return false;  // auto: only when most of the queue stays put
-    const int nchW = (int)cdiv(scan, kWinCh);
-    if (nchW == 0) return false;
-    if ((size_t)((c->W + 63) / 64 + 2) * 8 > (size_t)c->max_lds) return false;  // k_logscan's bitmap in LDS
-    const int nchB = (int)cdiv(c->l_E, kWinCh);
-    if (2 * nchB + nchW > kWinMaxCh) return false;
-    // room for the appends (backs, served workers with c > 1) behind the window
-    // (an underestimate only costs a rerun: k_emit_win flags a store past the buffer)
-    if (c->qoff + c->Qn + (int64_t)c->l_E + c->l_T + c->last_O + 1024 > c->qcap) return false;
-    c->l_nchW = nchW;
-    return true;
+    WindowIn w{};
+    w.win_cap = c->win_cap;
+    w.mode = c->win;
+    w.lists = c->ev_head != nullptr;
+    w.ev_ll = c->paths.ev_ll != 0;
+    w.compact = c->compact != 0;
+    w.purge_only = c->l_purge_only;
+    w.deque = c->deque != 0;
+    w.shard = c->shard != 0;
+    w.E = c->l_E;
+    w.W = c->W;
+    w.max_lds = c->max_lds;
+    w.last_L = c->last_L;
+    w.T = c->l_T;
+    w.last_O = c->last_O;
+    w.win_slack = c->win_slack;
+    w.Qn = c->Qn;
+    w.qoff = c->qoff;
+    w.qcap = c->qcap;
+    return plan_window(w, c->l_nchW);
 }
 
-// Enqueue every kernel of the tick described by c->l_* (events already on device).
-int enqueue_tick(fb_ctx *c) {
+// What plan_tick reads of the tick described by c->l_*.
+PlanIn plan_input(const fb_ctx *c) {
+    PlanIn in;
+    in.shard = c->shard;
+    in.phase = c->phase;
+    in.world = c->world;
+    in.deque = c->deque;
+    in.heartbeat = c->bud != nullptr;
+    in.lists = c->ev_head != nullptr;
+    in.qaos = c->qaos;
+    in.compact = c->compact;
+    in.cout = c->cout_slot != nullptr;
+    in.cout_cap = c->cout_cap;
+    in.cout_ecap = c->cout_ecap;
+    in.cout_ocap = c->cout_ocap;
+    in.W = c->W;
+    in.W_global = c->W_global;
+    in.E = c->l_E;
+    in.R = c->l_R;
+    in.head = c->l_head;
+    in.head_local = c->l_head_local;
+    in.Qn = c->l_Qn;
+    in.T = c->l_T;
+    in.ncu = c->ncu;
+    in.max_lds = c->max_lds;
+    in.win_occ = c->win_occ;
+    in.l_win = c->l_win;
+    in.l_nchW = c->l_nchW;
+    in.pos_ok = c->pos_ok;
+    in.l_resort = c->l_resort;
+    in.l_purge_only = c->l_purge_only;
+    in.stale_any = c->stale_any;
+    in.cm_pending = c->cm_pending;
+    in.cm_E = c->cm.E;
+    in.cm_win = c->cm.win;
+    in.cm_n_clr = c->cm.n_clr;
+    in.cm_shard = c->cm.shard;
+    in.cm_oseg = c->cm.oseg != nullptr;
+    in.cm_oseg_tiles = c->cm.oseg_tiles;
+    in.cm_n_orph = c->cm.n_orph;
+    in.knobs = c->paths;
+    return in;
+}
 
-    const int E = c->l_E;
-    const int W = c->W;
-    const int R = c->l_R;
-    const int64_t head = c->l_head, Qn = c->l_Qn;
-    const int64_t Qlog = Qn + 2 * (int64_t)E;
-    const int nbw = (int)std::max<int64_t>(1, cdiv(W, kBS));
-    // sharded: the log shard holds head_local entries (head is the global sequence)
-    const int nbf = (int)cdiv(c->shard ? c->l_head_local : head, kFTile);
-    const int nbq = (int)std::max<int64_t>(1, cdiv(Qlog, kBS));
-    int rc;
-    if ((rc = ensure_table(c, R, nbq))) return rc;
+// The message lists and status bytes of the tick: the context's own, or (sharded) the
+// regions of the bound exchange buffer.
+struct EvLists {
+    int32_t *front, *back;
+    uint8_t *evs;
+};
+
+// The arguments of the message kernels, linked lists or sort (c->link and c->lstamp are
+// this launch's).
+EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvLists &l) {
     const int cur = c->cur, nxt = 1 - cur;
-    // (fb_set_path("xplan", 0): large queues re-count in a phase-2 k_scan, no rows)
-    const bool xoff = !c->xplan_on && xrows_mode(c->world, R, Qlog) == 2;
-    const size_t xrb = (c->shard && !xoff) ? xrows_bytes(c->world, R, Qlog) : 0;
-    const size_t xgb = c->shard ? xgrows_bytes(c->world, R, Qlog) : 0;
-    const XLayout xl = xlayout(c->world, E, Qlog, xc_width(R), xrb, xgb);
-    int32_t *front = c->front_list, *back = c->back_list;
-    uint8_t *evs = c->ev_status;
-    if (c->shard) {
-        if (!c->xbuf || c->xcap < (int64_t)xl.total)
-            return fail(c, FB_ESTATE, "sharded tick needs an exchange buffer of %zu bytes (bound: %lld)", xl.total,
-                        (long long)c->xcap);
-        front = (int32_t *)(c->xbuf + xl.front);
-        back = (int32_t *)(c->xbuf + xl.back);
-        evs = c->xbuf + xl.evs;
-        // (an idle tick whose records the last phase 2 zeroed has nothing else to clear)
-        if (c->phase != 2 && !(E == 0 && c->xz_ok)) HIPCHK(c, hipMemsetAsync(c->xbuf, 0, xl.c8, c->stream));
+    const bool defer = c->bud != nullptr;  // one-GPU heartbeat context
+    EvArgs ea{};
+    ea.E = a.E;
+    ea.W = a.W;
+    ea.tick = c->tick;
+    ea.tte = c->l_tte;
+    ea.head_in = a.head_in;
+    ea.ev_kind = c->ev_kind;
+    ea.ev_val = c->ev_val;
+    ea.ev_ts = c->ev_ts;
+    ea.ev_seq = c->ev_seq;
+    ea.ev_status = l.evs;
+    ea.reg = c->reg;
+    ea.free_in = c->free_[cur];
+    ea.hb = c->hb;
+    ea.epoch = c->epoch;
+    ea.live_chk = a.live_chk;
+    ea.log_slot = c->log_slot;
+    ea.post = c->post;
+    ea.post_rf = c->post_rf;
+    ea.touched = c->touched;
+    ea.tbits = c->tbits;
+    ea.front_list = l.front;
+    ea.back_list = l.back;
+    // (the budget arrays exist together: all null without them)
+    ea.defer_clr = defer ? 1 : 0;
+    ea.ev_clr = c->ev_clr;
+    ea.ctag = c->ctag;
+    ea.lstamp = defer ? c->lstamp : 0;
+    ea.bud = c->bud;
+    ea.post_infl = c->post_infl;
+    if (p.grouping == Grouping::sort) {
+        ea.deque = c->deque;
+        ea.tokcnt_in = c->tokcnt[cur];
+        ea.front_rank = c->front_rank;
+        ea.back_rank = c->back_rank;
+        ea.post_tok = c->post_tok;
+        ea.post_nf = c->post_nf;
+        ea.shard = c->shard;
+        ea.slot_base = c->slot_base;
+        ea.head_local = c->l_head_local;
+        ea.lseq = c->lseq;
+        // the last pass's output
+        ea.skeys = c->keys[(p.passes - 1) & 1];
+        ea.svals = c->vals[(p.passes - 1) & 1];
+        return ea;
     }
-    TickArgs a{};
-    // lazy clears: the live test once entries of dead registrations may remain
-    a.live_chk = (lazy_ctx(c) && c->stale_any) ? 1 : 0;
+    ea.tbits_words = c->tbits ? (int)cdiv(a.W, 32) : 0;
+    ea.ev_slot = c->ev_slot;
+    ea.ev_head = c->ev_head;
+    ea.ev_next = c->ev_next;
+    ea.check_ev = c->l_chk[0] != nullptr;
+#ifdef FAASBAL_STAMPS
+    ea.dbg = c->dbg;
+#endif
+    ea.bad_min = c->bad_min;
+    ea.link = c->link;
+    ea.hout = c->hout_dev;
+    ea.lstamp = c->lstamp;
+    ea.bud_next = c->bud_next;
+    ea.orph_grp = a.f_emit ? 1 : 0;
+    if (p.commit == CommitPlan::in_ev_link) {  // the previous tick's commit rides in this launch
+        ea.cm = c->cm;
+        ea.cm_blocks = c->cm_grid;
+    }
+    // the slot purge (k_scan's W role) runs in k_ev_apply_ll's launch
+    ea.nbw = a.nbw;
+    ea.wtiles = p.ev_wtiles;
+    ea.now = c->l_now;
+    ea.st = c->st;
+    ea.free_out = c->free_[nxt];
+    ea.dmask = (!a.slots_in_scan || a.f_sep || a.f_emit || a.win) ? c->dmask : nullptr;
+    if (a.win) {  // k_emit_win's look-back granules and ticket start from zero
+        ea.wpart = c->wpart;
+        ea.died_tag = c->died_tag;
+        ea.wlb = c->wlb;
+        ea.wlb_n = a.nchB + a.nchF + a.nchW;
+        ea.wticket = c->wticket;
+        ea.cw = c->cw;
+    }
+    ea.wcnt = c->wcnt;
+    ea.grp = a.grp_on ? a.grp : nullptr;
+    ea.ngrp = a.ngrp;
+    ea.gstride = a.gstride;
+    ea.R = a.R;
+    return ea;
+}
+
+// The buffers and scalars of the tick kernels around the flags plan_tick chose (group rows
+// and, stamps builds, c->dbg are the driver's: they move state).
+void fill_tick_args(const fb_ctx *c, const TickPlan &p, const EvLists &l, TickArgs &a) {
+    const int cur = c->cur, nxt = 1 - cur;
     a.epoch = c->epoch;
     a.fault_qlen = -1;
-    a.W = W;
-    a.E = E;
-    a.R = R;
-    a.nbw = nbw;
-    a.nbf = c->deque ? 0 : nbf;  // start(): nobody dies, no log scan
-    a.nbq = nbq;
-    a.deque = c->deque;
-    a.redist = c->l_purge_only ? 0 : 1;
     a.q_cap = c->Wq_cap;
     a.tokcnt_in = c->tokcnt[cur];
     a.xw_in = c->xw[cur];
@@ -790,251 +818,16 @@ int enqueue_tick(fb_ctx *c) {
     a.xw_out = c->xw[nxt];
     a.kl_out = c->kl[nxt];
     a.qrank_out = c->qrank[nxt];
-    // small round tables: k_emit derives the cross-block prefixes itself (2 launches per tick)
-    // fused: k_emit2 reduces the (small) round table in every block, no k_plan launch
-    a.fused = (!c->shard && !c->force_plan && R <= kRFused && (int64_t)nbq * R <= (int64_t)kTabLd * kBS * 4) ? 1 : 0;
-    // large tables with R <= 128: k_emit2 after k_plan (fb_set_path("plan", 2): the chunked k_emit)
-    a.segw = (!c->shard && R <= kRFused && c->force_plan != 2) ? 1 : 0;
-    // large tables for k_emit2: group rows too, scanned by k_plan2
-    const bool gplan = !a.fused && a.segw && !c->shard;
-    // sharded phase 2 with a round table of <= 128 rows: group rows instead of k_plan
-    const bool sgrp = c->shard && c->phase == 2 && R <= kRFused && !xrb;
-    if ((a.fused || gplan || sgrp) && !c->l_win) {  // (a window tick uses no group rows)
-        // group rows: fused / sharded, about sqrt(nbq) groups of 2^gshift queue blocks (the
-        // emit reads both); k_plan2, the smallest groups that make at most 64 rows (one
-        // workgroup each)
-        int gs = 0;
-        if (a.fused || sgrp)
-            while ((1 << (2 * gs)) < nbq || cdiv(nbq, (int64_t)1 << gs) > 64) ++gs;
-        else
-            while (cdiv(nbq, (int64_t)1 << gs) > 64) ++gs;
-        a.grp_on = 1;
-        a.gshift = gs;
-        a.gstride = sgrp ? 2 * R + 4 : R + 4;
-        a.ngrp = (int)cdiv(nbq, 1 << gs);
-        if (a.ngrp > 64 || (int64_t)a.ngrp * a.gstride > kGrpWords)
-            return fail(c, FB_ERANGE, "group rows (%d x %d words) exceed the reservation", a.ngrp, a.gstride);
-        c->gpar ^= 1;
-        a.grp = c->grp[c->gpar];  // zero: its last user's k_emit2 cleared it
-        a.grp_zero = c->grp[c->gpar ^ 1];
-        a.zero_words = c->gdirty[c->gpar ^ 1];
-        c->gdirty[c->gpar ^ 1] = 0;
-        c->gdirty[c->gpar] = a.ngrp * a.gstride;
-    }
-    if (++c->lstamp == 0) c->lstamp = 1;  // every launch (reruns included) stamps its own
-    const bool defer = c->bud != nullptr;  // one-GPU heartbeat context
-    a.lds_bitmap = W <= kLdsBitmapSlots ? 1 : 0;
-    if (defer) {
+    if (c->bud) {  // one-GPU heartbeat context
         a.bud = c->bud;
         a.bud_next = c->bud_next;
         a.post_infl = c->post_infl;
         a.ctag = c->ctag;
         a.lstamp = c->lstamp;
     }
-    // the log scan gathers one 16-byte record per in-flight entry; past 128K slots
-    // (2 MB of records) those gathers miss L2, so k_slots first writes the
-    // died bitmap (W/8 bytes, L2-resident) and the scan tests bits instead
-    a.slots_in_scan = (c->split_slots > 0 || (c->split_slots < 0 && W > kLdsBitmapSlots)) ? 0 : 1;
-    // ... or better, while the bitmap fits in one workgroup's LDS: the W-role of
-    // k_scan writes it and k_logscan tests every entry against an LDS copy
-    const size_t bm_bytes = (size_t)(((W + 63) / 64 + 1) / 2 + 1) * 16;
-    a.f_sep = (head > 0 && !c->deque && (c->logscan > 0 || (c->logscan < 0 && W > kLdsBitmapSlots)) &&
-               bm_bytes <= (size_t)c->max_lds && !(c->shard && c->phase == 2)) ? 1 : 0;
-    if (a.f_sep) a.slots_in_scan = 1;
-    // fused one-GPU ticks: O from the slot purge's in-flight counts, the orphans flagged
-    // and compacted by k_emit2's log workgroups (k_scan without log blocks); not when the
-    // log role was asked to run as k_logscan (fb_set_path("logscan", 1))
-    const int nbfe = (int)cdiv(nbf, 4);
-    const size_t bm16 = (size_t)(((W + 63) / 64 + 1) / 2) * 16;
-    a.f_emit = (defer && a.fused && !a.f_sep && W <= kLdsBitmapSlots && nbfe <= kFEmitMaxBlocks &&
-                bm16 <= (size_t)c->max_lds && !c->l_win) ? 1 : 0;
-    c->l_oseg = a.f_emit != 0 || c->l_win;
-    c->l_nbf = nbf;
-    c->evict_ok = false;
-    c->dense_ok = false;
-    const int ls_grid = std::max(1, std::min(c->ncu, (int)cdiv(nbf, kLsBS / 64)));
-    c->l_used_ll = false;
-    const bool ll = E > 0 && c->ev_head && c->ev_ll && !c->l_resort;
-    if (c->l_win && !c->pos_ok) {
-        // the first window tick after general ticks: every queued slot's position, once
-        launch_pos_rebuild(c->pos_of[c->qcur], c->queue[c->qcur], c->qfree[c->qcur], c->qoff, Qn, Stream(c->stream));
-        c->pos_ok = true;
-    }
-    // the last tick's deferred commit: into this launch's first kernel (k_ev_link below, or
-    // k_scan for an idle tick after an idle tick), else as its own launch now
-    const bool cm_idle = c->cm_pending && c->cm.E == 0 && !c->cm.win && c->cm.n_clr == 0 && !c->cm.shard;
-    if (!ll && !(E == 0 && cm_idle) && (rc = flush_commit(c))) return rc;
-    if (ll) {
-        // group the messages per slot by linked lists (no sort): two launches
-        EvArgs ea{};
-        ea.E = E;
-        ea.W = W;
-        ea.tick = c->tick;
-        ea.tte = c->l_tte;
-        ea.head_in = head;
-        ea.ev_kind = c->ev_kind;
-        ea.ev_val = c->ev_val;
-        ea.ev_ts = c->ev_ts;
-        ea.ev_seq = c->ev_seq;
-        ea.ev_status = evs;
-        ea.reg = c->reg;
-        ea.free_in = c->free_[cur];
-        ea.hb = c->hb;
-        ea.epoch = c->epoch;
-        ea.live_chk = (lazy_ctx(c) && c->stale_any) ? 1 : 0;
-        ea.log_slot = c->log_slot;
-        ea.post = c->post;
-        ea.post_rf = c->post_rf;
-        ea.touched = c->touched;
-        ea.tbits = c->tbits;
-        ea.tbits_words = c->tbits ? (int)cdiv(W, 32) : 0;
-        ea.front_list = front;
-        ea.back_list = back;
-        ea.ev_slot = c->ev_slot;
-        ea.ev_head = c->ev_head;
-        ea.ev_next = c->ev_next;
-        ea.check_ev = c->l_chk[0] != nullptr;
-#ifdef FAASBAL_STAMPS
-        ea.dbg = c->dbg;
-#endif
-        ea.bad_min = c->bad_min;
-        if (++c->link == 0) c->link = 1;  // a fresh stamp per launch, reruns included
-        ea.link = c->link;
-        ea.hout = c->hout_dev;
-        ea.defer_clr = defer ? 1 : 0;
-        ea.ev_clr = c->ev_clr;
-        ea.ctag = c->ctag;
-        ea.lstamp = c->lstamp;
-        ea.bud = c->bud;
-        ea.post_infl = c->post_infl;
-        ea.bud_next = c->bud_next;
-        ea.orph_grp = a.f_emit ? 1 : 0;
-        if (c->cm_pending) {  // the previous tick's commit rides in this launch
-            ea.cm = c->cm;
-            ea.cm_blocks = c->cm_grid;
-            c->cm_pending = false;
-        }
-        // the slot purge (k_scan's W role) runs in k_ev_apply_ll's launch: extra blocks for
-        // the untouched slots, each owner thread for its touched slot
-        ea.nbw = nbw;
-        ea.wtiles = c->wtiles ? c->wtiles : (nbw >= 1024 ? 4 : 1);
-        ea.now = c->l_now;
-        ea.st = c->st;
-        ea.free_out = c->free_[nxt];
-        ea.dmask = (!a.slots_in_scan || a.f_sep || a.f_emit || c->l_win) ? c->dmask : nullptr;
-        ea.wpart = c->l_win ? c->wpart : nullptr;
-        ea.died_tag = c->l_win ? c->died_tag : nullptr;
-        if (c->l_win) {  // k_emit_win's look-back granules and ticket start from zero
-            ea.wlb = c->wlb;
-            ea.wlb_n = 2 * (int)cdiv(E, kWinCh) + c->l_nchW;
-            ea.wticket = c->wticket;
-            ea.cw = c->cw;
-        }
-        ea.wcnt = c->wcnt;
-        ea.grp = a.grp_on ? a.grp : nullptr;
-        ea.ngrp = a.ngrp;
-        ea.gstride = a.gstride;
-        ea.R = R;
-        c->l_used_ll = true;
-        {
-            Timer t(c, "ev_link");
-            launch_ev_link(ea, t.st());
-        }
-        Timer t(c, "ev_apply");
-        launch_ev_apply_ll(ea, t.st());
-    } else if (E > 0 && !(c->shard && c->phase == 2)) {
-
-        // stable radix sort of events by slot
-        int bits = 1;
-        while ((1ll << bits) < (int64_t)(c->shard ? c->W_global : W)) ++bits;
-        const int nb = (int)cdiv(E, kRsTile);
-        // digits of up to 11 bits while the batch is small enough for the scatter's
-        // table walk (1 M workers: two passes of 10 bits instead of three of 8)
-        const bool wide = c->rs_wide && nb <= kRsWideMaxBlocks;
-        const int passes = wide ? (bits + 10) / 11 : (bits + 7) / 8;
-        const int db = wide ? (bits + passes - 1) / passes : 8;
-        if (passes > 4) return fail(c, FB_ERANGE, "event sort of %d passes", passes);
-        const int NBw = db <= 8 ? 256 : db <= 10 ? 1024 : 2048;
-        const uint32_t *kin = (const uint32_t *)c->ev_slot, *vin = nullptr;
-        for (int ps = 0; ps < passes; ++ps) {
-            Timer t(c, "rs_sort");
-            RsPass p{};
-            p.kin = kin;
-            p.vin = vin;
-            p.kout = c->keys[ps & 1];
-            p.vout = c->vals[ps & 1];
-            p.n = E;
-            p.shift = db * ps;
-            p.db = db;
-            p.nblk = nb;
-            p.hist = c->rs_hist[0];
-            p.identity_vals = ps == 0 ? 1 : 0;
-            if (ps == 0 && !c->shard) {
-                // pass 0 also clears the one-GPU front / back lists (sharded: zeroed with the
-                // exchange buffer) and the touched bitmap
-                p.zero0 = front;
-                p.zero1 = back;
-                p.zbits = c->tbits;
-                p.zwords = c->tbits ? (int)cdiv(W, 32) : 0;
-            }
-            launch_rs_pass(p, t.first(), t.last());
-            kin = p.kout;
-            vin = p.vout;
-        }
-        EvArgs a{};
-        a.E = E;
-        a.deque = c->deque;
-        a.tokcnt_in = c->tokcnt[cur];
-        a.front_rank = c->front_rank;
-        a.back_rank = c->back_rank;
-        a.post_tok = c->post_tok;
-        a.post_nf = c->post_nf;
-        a.shard = c->shard;
-        a.slot_base = c->slot_base;
-        a.W = W;
-        a.head_local = c->l_head_local;
-        a.lseq = c->lseq;
-        a.tick = c->tick;
-        a.tte = c->l_tte;
-        a.head_in = head;
-        a.skeys = kin;
-        a.svals = vin;
-        a.ev_kind = c->ev_kind;
-        a.ev_val = c->ev_val;
-        a.ev_ts = c->ev_ts;
-        a.ev_seq = c->ev_seq;
-        a.ev_status = evs;
-        a.reg = c->reg;
-        a.free_in = c->free_[cur];
-        a.hb = c->hb;
-        a.epoch = c->epoch;
-        a.live_chk = (lazy_ctx(c) && c->stale_any) ? 1 : 0;
-        a.log_slot = c->log_slot;
-        a.post = c->post;
-        a.post_rf = c->post_rf;
-        a.touched = c->touched;
-        a.tbits = c->tbits;
-        a.front_list = front;
-        a.back_list = back;
-        if (defer) {
-            a.defer_clr = 1;
-            a.ev_clr = c->ev_clr;
-            a.ctag = c->ctag;
-            a.lstamp = c->lstamp;
-            a.bud = c->bud;
-            a.post_infl = c->post_infl;
-        }
-        Timer t(c, "ev_apply");
-        launch_ev_apply(a, t.st());
-    }
-    a.slots_in_apply = c->l_used_ll ? 1 : 0;
     a.tick = c->tick;
     a.now = c->l_now;
     a.tte = c->l_tte;
-    a.Qn = Qn;
-    a.Qlog = Qlog;
-    a.head_in = head;
-    a.T = c->l_T;
     a.log_cap = c->log_cap;
     a.reg = c->reg;
     a.hb = c->hb;
@@ -1042,18 +835,14 @@ int enqueue_tick(fb_ctx *c) {
     // the committed queue: the window [qoff, qoff + Qn) of the current queue buffers
     const int qc = c->qcur, qn = c->qcur ^ 1;
     a.queue_in = c->queue[qc] + c->qoff;
-    a.qaos = (!c->shard && c->qaos) ? 1 : 0;
-    a.cq_direct = (E == 0 && a.qaos && a.segw && !c->deque) ? 1 : 0;
     a.qfree_in = c->qfree[qc] ? c->qfree[qc] + c->qoff : nullptr;
     a.qhb_in = c->qhb[qc] ? c->qhb[qc] + c->qoff : nullptr;
     a.touched = c->touched;
     a.tbits = c->tbits;
     a.post = c->post;
     a.post_rf = c->post_rf;
-    // past the L2-resident sizes the purge is bandwidth-bound: skip untouched post records
-    a.post_lazy = W > kLdsBitmapSlots ? 1 : 0;
-    a.front_list = front;
-    a.back_list = back;
+    a.front_list = l.front;
+    a.back_list = l.back;
     a.st = c->st;
     a.dmask = c->dmask;
     a.c_arr = c->c_arr;
@@ -1072,18 +861,12 @@ int enqueue_tick(fb_ctx *c) {
     a.P = c->P;
     a.A_rep = c->A_rep;
     a.P_rep = c->P_rep;
-    a.repl = gplan ? 1 : 0;  // k_plan2 writes a copy per group
     a.trash = c->trash;
-    c->l_compact = c->compact && !c->shard;
-    if (c->l_compact) {
+    if (p.l_compact) {
         a.rb_slot = c->rb_slot;
         a.rb_c = c->rb_c;
     }
-    // registered pinned outputs: the compact form and the evicted slots go straight to the
-    // host (fused ticks, whose orphans a gather launch after the emission sends there too)
-    c->l_cout = c->l_compact && c->cout_slot && a.fused && a.f_emit && Qlog <= c->cout_cap && W <= c->cout_ecap &&
-                head <= c->cout_ocap;
-    if (c->l_cout) {
+    if (p.l_cout) {
         a.rb_slot = c->cout_slot;
         a.rb_c = c->cout_c;
     }
@@ -1094,43 +877,263 @@ int enqueue_tick(fb_ctx *c) {
     a.queue_out = c->queue[qn];
     a.qfree_out = c->qfree[qn];
     a.qhb_out = c->qhb[qn];
-
     a.c_hb = c->c_hb;
     a.orphans = c->orphans;
     // (registered pinned outputs: the evicted slots straight into the caller's array)
-    a.evicted = c->l_cout ? c->cout_ev : c->evicted;
+    a.evicted = p.l_cout ? c->cout_ev : c->evicted;
     a.hout = c->hout_dev;
     if (c->shard) {
-        a.shard = c->phase == 2 ? 2 : 1;
-        // (only while the log role is fused into k_scan: with k_logscan the slot blocks are
-        // the short ones)
-        a.wfirst = (a.shard == 1 && !a.f_sep && c->wfirst_on) ? 1 : 0;
-        // sharded phase 1: 4 slot tiles per workgroup while the log role has its own launch
-        // (N = 2 at configs[3]: scan 18.4 -> 17.8 us), 1 behind wfirst (N = 8: no gain)
-        if (a.shard == 1) a.wtiles = c->wtiles ? c->wtiles : (a.wfirst ? 1 : 4);
         a.slot_base = c->slot_base;
         a.rank = c->rank;
         a.world = c->world;
         a.head_local = c->l_head_local;
         a.lseq = c->lseq;
         a.lseq_out = c->lseq;
-        a.xc8 = c->xbuf + xl.c8;
-        a.xcw = xc_width(R);
+        a.xc8 = c->xbuf + p.xl.c8;
         // this tick's copy of the records; phase 2 with block rows zeroes the other
         const size_t xrw = (size_t)c->world * kXRecWords;
-        a.xrec = (unsigned long long *)(c->xbuf + xl.rec) + (size_t)c->xpar * xrw;
-        a.xrows = xrb ? c->xbuf + xl.rows : nullptr;
-        a.xplan = (c->xplan_on && xrows_mode(c->world, R, Qlog) == 2) ? 1 : 0;
-        // (<= 64 chunks of kXsBlocks queue blocks: 16 loads per k_emit_shard_xp thread)
-        a.xself = (a.xplan && c->xself_on && cdiv(Qlog, kBS) <= 64 * kXsBlocks) ? 1 : 0;
-        // k_emit_shard_xp's compaction workgroups first when they are many (configs[3], N = 2:
-        // 975 beside 1 774 queue workgroups, emit 30.3 -> 26.9 us; N = 8: 244, no gain)
-        a.xcfirst = (a.xplan && c->xcfirst_on &&
-                     4 * ((a.nbf + 3) / 4 + (a.nbw + 3) / 4) > (nbq + 1) / 2) ? 1 : 0;
+        a.xrec = (unsigned long long *)(c->xbuf + p.xl.rec) + (size_t)c->xpar * xrw;
+        a.xrows = p.xrb ? c->xbuf + p.xl.rows : nullptr;
+        if (c->l_full && c->phase == 2) a.assign_all = c->assign_all;
+        if (a.xplan) {
+            // k_xscan's outputs in the plan tables (unused on this path): per-block prefixes in
+            // qpre's words, the chunk prefixes and totals in opre's
+            a.xpre = reinterpret_cast<uint32_t *>(c->qpre);
+            a.xct = reinterpret_cast<uint32_t *>(c->opre);
+            a.xA = a.xct + (size_t)cdiv(a.nbq, kXsBlocks) * 2 * a.R;
+            a.xtk = c->xs_tk;
+        }
+        a.xgrows = p.xgb ? c->xbuf + p.xl.grows : nullptr;
+        a.xg_acc = c->xg_acc;
+        a.xg_tk = c->xg_tk;
+        a.ogrp = c->ogrp;
+        if ((p.xrb || a.xplan) && c->phase == 2) {
+            a.xz = (unsigned long long *)(c->xbuf + p.xl.rec) + (size_t)(c->xpar ^ 1) * xrw;
+            a.xz_words = (int)xrw;
+        }
+        a.ocnt = c->ocnt;
+        a.osegcnt = c->osegcnt;
+        a.opre = c->opre;
+        a.oA = c->oA;
+    }
+    if (a.win) {
+        a.wq_off = c->qoff;
+        a.wq_tail = c->qoff + a.Qn;
+        a.wq_cap = c->qcap;
+        a.q_cap = c->Wq_cap;  // the next window (tombstones included) must fit the general path
+        a.wq_buf = c->queue[qc];
+        a.wqf_buf = c->qfree[qc];
+        a.wqh_buf = c->qhb[qc];
+        a.wlb = c->wlb;
+        a.wticket = c->wticket;
+        a.cw = c->cw;
+        a.cw_tag = c->link;
+        a.wpart = c->wpart;
+        a.pos_in = c->pos_of[qc];
+        a.tomb = c->tomb;
+        a.lstamp = c->lstamp;
+        // (a test's injected length goes to the device, which checks what an eager commit reads)
+        a.fault_qlen = c->paths.fault_qlen;
+        a.lpart = c->lpart;
+        a.died_tag = c->died_tag;
+    }
+}
+
+// A stage that launches the same way in every tick kind: the window's position rebuild, the
+// last tick's commit as its own launch, the message grouping (ps: the sort pass, counted
+// here), k_slots, k_scan and k_logscan.
+int launch_common_stage(fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvArgs &ea, Stage s, int &ps) {
+    switch (s) {
+    case Stage::pos_rebuild:
+        // the first window tick after general ticks: every queued slot's position, once
+        launch_pos_rebuild(c->pos_of[c->qcur], c->queue[c->qcur], c->qfree[c->qcur], c->qoff, c->l_Qn,
+                           Stream(c->stream));
+        c->pos_ok = true;
+        return FB_OK;
+    case Stage::commit:
+        return flush_commit(c);
+    case Stage::ev_link: {
+        Timer t(c, "ev_link");
+        launch_ev_link(ea, t.st());
+        return FB_OK;
+    }
+    case Stage::ev_apply: {
+        Timer t(c, "ev_apply");
+        if (p.grouping == Grouping::lists) launch_ev_apply_ll(ea, t.st());
+        else launch_ev_apply(ea, t.st());
+        return FB_OK;
+    }
+    case Stage::rs_sort: {
+        Timer t(c, "rs_sort");
+        RsPass r{};
+        r.kin = ps == 0 ? (const uint32_t *)c->ev_slot : c->keys[(ps - 1) & 1];
+        r.vin = ps == 0 ? nullptr : c->vals[(ps - 1) & 1];
+        r.kout = c->keys[ps & 1];
+        r.vout = c->vals[ps & 1];
+        r.n = ea.E;
+        r.shift = p.db * ps;
+        r.db = p.db;
+        r.nblk = p.rs_blocks;
+        r.hist = c->rs_hist[0];
+        r.identity_vals = ps == 0 ? 1 : 0;
+        if (ps == 0 && !c->shard) {
+            // pass 0 also clears the one-GPU front / back lists (sharded: zeroed with the
+            // exchange buffer) and the touched bitmap
+            r.zero0 = ea.front_list;
+            r.zero1 = ea.back_list;
+            r.zbits = c->tbits;
+            r.zwords = c->tbits ? (int)cdiv(ea.W, 32) : 0;
+        }
+        launch_rs_pass(r, t.first(), t.last());
+        ++ps;
+        return FB_OK;
+    }
+    case Stage::slots: {
+        Timer t(c, "slots");
+        launch_slots(a, t.st());
+        return FB_OK;
+    }
+    case Stage::scan: {
+        Timer t(c, "scan");
+        launch_scan(a, t.st());
+        return FB_OK;
+    }
+    case Stage::logscan: {
+        Timer t(c, "logscan");
+        launch_logscan(a, p.ls_grid, t.st());
+        return FB_OK;
+    }
+    default:
+        return fail(c, FB_EHIP, "launch plan: stage %s has no place in this tick", stage_name(s));
+    }
+}
+
+int launch_window_tick(fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvArgs &ea) {
+    int ps = 0;
+    for (int i = 0; i < p.n_stages; ++i) {
+        if (p.stages[i] == Stage::emit) {
+            Timer t(c, "emit");
+            // an eager commit follows: the launch's own completion signal is the event the
+            // host waits for (a separate event record between the two kernels cost ~6 us)
+            c->tick_ev_set = !c->timing && c->eager && c->reruns == 0;
+            launch_emit_win(a, a.nchB + a.nchF + a.nchW,
+                            c->tick_ev_set ? Stream(c->stream, nullptr, c->tick_ev) : t.st());
+        } else if (int rc = launch_common_stage(c, p, a, ea, p.stages[i], ps)) {
+            return rc;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return FB_OK;
+}
+
+// Phase 1: own slots' purge, orphan flags and free counts into the exchange buffer.
+int launch_shard_phase1(fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvArgs &ea) {
+    int ps = 0;
+    for (int i = 0; i < p.n_stages; ++i)
+        if (int rc = launch_common_stage(c, p, a, ea, p.stages[i], ps)) return rc;
+    HIPCHK(c, hipGetLastError());
+    return FB_OK;
+}
+
+int launch_shard_phase2(fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvArgs &ea) {
+    // with exchanged block rows k_emit_shard also zeroes the other records copy, which the
+    // next tick's phase 1 writes; else the next phase 1 clears the records
+    const bool rows = a.xrows || a.xplan;
+    if (!rows) c->xz_ok = false;
+    int ps = 0;
+    for (int i = 0; i < p.n_stages; ++i) {
+        const Stage s = p.stages[i];
+        if (s == Stage::scan2) {
+            Timer t(c, "scan2");
+            launch_scan(a, t.st());
+        } else if (s == Stage::plan) {
+            Timer t(c, "plan");
+            if (a.xplan) launch_xscan(a, t.st());
+            else launch_plan(a, t.st());
+        } else if (s == Stage::emit) {
+            Timer t(c, "emit");
+            launch_emit_shard(a, t.st());
+        } else if (int rc = launch_common_stage(c, p, a, ea, s, ps)) {
+            return rc;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    if (rows) {
+        c->xpar ^= 1;
+        c->xz_ok = true;
+    }
+    return FB_OK;
+}
+
+int launch_local_tick(fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvArgs &ea) {
+    int ps = 0;
+    for (int i = 0; i < p.n_stages; ++i) {
+        const Stage s = p.stages[i];
+        if (s == Stage::plan) {
+            Timer t(c, "plan");
+            launch_plan(a, t.st());
+        } else if (s == Stage::emit) {
+            Timer t(c, "emit");
+            if (a.segw) launch_emit2(a, t.st());
+            else launch_emit(a, t.st());
+        } else if (s == Stage::orph_gather) {
+            launch_orph_gather(c->cout_orph, c->orphans, c->fcnt, c->l_nbf, Stream(c->stream));
+        } else if (int rc = launch_common_stage(c, p, a, ea, s, ps)) {
+            return rc;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return FB_OK;
+}
+
+// Enqueue every kernel of the tick described by c->l_* (events already on device): the
+// plan (plan_tick: every rule that picks the launches), the state the launch moves, the
+// kernels' arguments, then the tick kind's launch sequence.
+int enqueue_tick(fb_ctx *c) {
+    int rc;
+    TickArgs a{};
+    TickPlan p;
+    plan_tick(plan_input(c), a, p);
+    if ((rc = ensure_table(c, a.R, a.nbq))) return rc;
+    if (p.err == PlanError::group_rows)
+        return fail(c, FB_ERANGE, "group rows (%d x %d words) exceed the reservation", a.ngrp, a.gstride);
+    if (p.err == PlanError::sort_passes) return fail(c, FB_ERANGE, "event sort of %d passes", p.passes);
+    if (p.err == PlanError::shard_rows)
+        return fail(c, FB_ERANGE, "sharded tick: round table of %d rows (limit %d)", a.R, kShardMaxR);
+
+    EvLists l{c->front_list, c->back_list, c->ev_status};
+    if (c->shard) {
+        if (!c->xbuf || c->xcap < (int64_t)p.xl.total)
+            return fail(c, FB_ESTATE, "sharded tick needs an exchange buffer of %zu bytes (bound: %lld)", p.xl.total,
+                        (long long)c->xcap);
+        l.front = (int32_t *)(c->xbuf + p.xl.front);
+        l.back = (int32_t *)(c->xbuf + p.xl.back);
+        l.evs = c->xbuf + p.xl.evs;
+        // (an idle tick whose records the last phase 2 zeroed has nothing else to clear)
+        if (c->phase != 2 && !(a.E == 0 && c->xz_ok)) HIPCHK(c, hipMemsetAsync(c->xbuf, 0, p.xl.c8, c->stream));
+    }
+    if (a.grp_on) {
+        c->gpar ^= 1;
+        a.grp = c->grp[c->gpar];  // zero: its last user's k_emit2 cleared it
+        a.grp_zero = c->grp[c->gpar ^ 1];
+        a.zero_words = c->gdirty[c->gpar ^ 1];
+        c->gdirty[c->gpar ^ 1] = 0;
+        c->gdirty[c->gpar] = a.ngrp * a.gstride;
+    }
+    if (++c->lstamp == 0) c->lstamp = 1;  // every launch (reruns included) stamps its own
+    c->l_oseg = p.l_oseg;
+    c->l_nbf = p.nbf;
+    c->evict_ok = false;
+    c->dense_ok = false;
+    c->l_used_ll = p.grouping == Grouping::lists;
+    if (c->l_used_ll && ++c->link == 0) c->link = 1;  // a fresh stamp per k_ev_link launch, reruns included
+    c->l_compact = p.l_compact;
+    c->l_cout = p.l_cout;
+    if (c->shard) {
         c->l_full = c->full_assign != 0;
         if (c->l_full && c->phase == 2) {
             // the whole tick's assignments: at most its pending tasks plus every in-flight entry
-            const int64_t need = std::max<int64_t>(1, c->l_T + head);
+            const int64_t need = std::max<int64_t>(1, c->l_T + c->l_head);
             if (need > c->assign_cap) {
                 const int64_t cap = std::max(need, 2 * c->assign_cap);
                 HIPCHK(c, stream_wait(c));
@@ -1140,35 +1143,14 @@ int enqueue_tick(fb_ctx *c) {
                 if ((rc = dalloc(c, &c->assign_all, (size_t)cap))) return rc;
                 c->assign_cap = cap;
             }
-            a.assign_all = c->assign_all;
         }
-        if (a.xplan) {
-            // k_xscan's outputs in the plan tables (unused on this path): per-block prefixes in
-            // qpre's words, the chunk prefixes and totals in opre's
-            a.xpre = reinterpret_cast<uint32_t *>(c->qpre);
-            a.xct = reinterpret_cast<uint32_t *>(c->opre);
-            a.xA = a.xct + (size_t)cdiv(nbq, kXsBlocks) * 2 * R;
-            a.xtk = c->xs_tk;
-        }
-        a.xgrows = xgb ? c->xbuf + xl.grows : nullptr;
-        a.xg_acc = c->xg_acc;
-        a.xg_tk = c->xg_tk;
-        a.ogrp = c->ogrp;
-        if ((xrb || a.xplan) && c->phase == 2) {
-            a.xz = (unsigned long long *)(c->xbuf + xl.rec) + (size_t)(c->xpar ^ 1) * xrw;
-            a.xz_words = (int)xrw;
-        }
-        a.ocnt = c->ocnt;
-        a.osegcnt = c->osegcnt;
-        a.opre = c->opre;
-        a.oA = c->oA;
     }
 #ifdef FAASBAL_STAMPS
     {
         // diagnostic stamp rows (stamps builds only); grown geometrically -- hipFree
         // synchronises the device
         // (k_emit_win stamps rows from 8192 on, one per chunk)
-        const size_t need = std::max((size_t)4 * (nbw + nbf + nbq) * 16 + 16, (size_t)(8192 + kWinMaxCh) * 16);
+        const size_t need = std::max((size_t)4 * (a.nbw + c->l_nbf + a.nbq) * 16 + 16, (size_t)(8192 + kWinMaxCh) * 16);
         if (need > c->dbg_n) {
             HIPCHK(c, stream_wait(c));
             hipFree(c->dbg);
@@ -1180,162 +1162,16 @@ int enqueue_tick(fb_ctx *c) {
         a.dbg = c->dbg;
     }
 #endif
-    if (c->l_win) {
-        // window tick (E > 0, purge in the apply launch): k_logscan writes the orphans into
-        // per-tile segments and a partial count per workgroup (nothing, when no registration
-        // died: died_tag); k_emit_win counts the chunks of [backs][fronts][window prefix] by
-        // decoupled look-back, serves, appends and reports the window
-        a.win = 1;
-        a.wseg = 1;
-        a.nbf = nbf;
-        a.wq_off = c->qoff;
-        a.wq_tail = c->qoff + Qn;
-        a.wq_cap = c->qcap;
-        a.q_cap = c->Wq_cap;  // the next window (tombstones included) must fit the general path
-        a.wq_buf = c->queue[qc];
-        a.wqf_buf = c->qfree[qc];
-        a.wqh_buf = c->qhb[qc];
-        a.nchB = (int)cdiv(E, kWinCh);
-        a.nchF = a.nchB;
-        a.nchW = c->l_nchW;
-        a.wlb = c->wlb;
-        a.wticket = c->wticket;
-        a.cw = c->cw;
-        a.cw_tag = c->link;
-        a.wpart = c->wpart;
-        a.pos_in = c->pos_of[qc];
-        a.tomb = c->tomb;
-        a.lstamp = c->lstamp;
-        // (a test's injected length goes to the device, which checks what an eager commit reads)
-        a.fault_qlen = c->fault_qlen;
-        const int nch = a.nchB + a.nchF + a.nchW;
-        // few enough chunks to be resident together: chunk = workgroup index, no ticket round
-        // before the element loads.  A chunk's look-back waits on lower chunks only, so the
-        // direct form needs every lower-indexed workgroup resident or done -- guaranteed while
-        // the whole grid fits at once (the occupancy calculator's workgroups per CU, context
-        // creation), with half of it left to concurrent work on the device
-        a.win_direct = (c->win_direct && 2 * (int64_t)nch <= (int64_t)c->win_occ * c->ncu) ? 1 : 0;
-        a.lpart = c->lpart;
-        a.died_tag = c->died_tag;
-        a.n_lpart = head > 0 ? ls_grid : 0;
-        if (head > 0) {
-            Timer t(c, "logscan");
-            launch_logscan(a, ls_grid, t.st());
-        }
-        {
-            Timer t(c, "emit");
-            // an eager commit follows: the launch's own completion signal is the event the
-            // host waits for (a separate event record between the two kernels cost ~6 us)
-            c->tick_ev_set = !c->timing && c->eager && c->reruns == 0;
-            launch_emit_win(a, nch, c->tick_ev_set ? Stream(c->stream, nullptr, c->tick_ev) : t.st());
-        }
-        HIPCHK(c, hipGetLastError());
-        return FB_OK;
+    fill_tick_args(c, p, l, a);
+    const EvArgs ea = p.grouping == Grouping::none ? EvArgs{} : fill_ev_args(c, p, a, l);
+    // the last tick's commit, when this tick's first kernel runs it
+    if (p.commit == CommitPlan::in_ev_link || p.commit == CommitPlan::in_scan) c->cm_pending = false;
+    switch (p.kind) {
+    case TickKind::window: return launch_window_tick(c, p, a, ea);
+    case TickKind::shard_phase1: return launch_shard_phase1(c, p, a, ea);
+    case TickKind::shard_phase2: return launch_shard_phase2(c, p, a, ea);
+    default: return launch_local_tick(c, p, a, ea);
     }
-    if (a.shard == 1) {
-        // phase 1: own slots' purge, orphan flags and free counts into the exchange buffer
-        if (!a.slots_in_scan) {
-            Timer t(c, "slots");
-            launch_slots(a, t.st());
-        }
-        {
-            Timer t(c, "scan");
-            launch_scan(a, t.st());
-        }
-        if (a.f_sep) {
-            Timer t(c, "logscan");
-            launch_logscan(a, ls_grid, t.st());
-        }
-        HIPCHK(c, hipGetLastError());
-        return FB_OK;
-    }
-    if (a.shard == 2) {
-        if (R > kShardMaxR) return fail(c, FB_ERANGE, "sharded tick: round table of %d rows (limit %d)", R, kShardMaxR);
-        if (a.xrows || a.xplan) {
-            // exchanged block rows: k_emit_shard alone (it also zeroes the other records copy,
-            // which the next tick's phase 1 writes); xplan: k_xscan's counts and prefixes of the
-            // exchanged c bytes first
-            if (a.xplan) {
-                Timer t(c, "plan");
-                launch_xscan(a, t.st());
-            }
-            Timer t(c, "emit");
-            launch_emit_shard(a, t.st());
-            HIPCHK(c, hipGetLastError());
-            c->xpar ^= 1;
-            c->xz_ok = true;
-            return FB_OK;
-        }
-        c->xz_ok = false;  // the next phase 1 clears the records
-        {
-            Timer t(c, "scan2");
-            launch_scan(a, t.st());
-        }
-        if (!a.grp_on) {  // wide tables: k_plan's column scans
-            Timer t(c, "plan");
-            launch_plan(a, t.st());
-        }
-        Timer t(c, "emit");
-        launch_emit_shard(a, t.st());
-        HIPCHK(c, hipGetLastError());
-        return FB_OK;
-    }
-    a.free_pre = (a.segw && a.slots_in_scan && !a.slots_in_apply && !c->deque && !c->l_win) ? 1 : 0;
-    if (c->cm_pending) {
-        // an idle tick's commit (evicted records, orphaned log entries) rides in k_scan when
-        // k_scan purges the slots and reads no log entry itself
-        // (per-tile orphan segments are cleared by k_emit2's log workgroups, tile by tile)
-        const bool seg_ok = !c->cm.oseg || (a.f_emit && c->cm.oseg_tiles <= nbf);
-        if (a.slots_in_scan && !a.slots_in_apply && (a.f_emit || a.f_sep) && !c->deque && seg_ok) {
-            a.cm_fold = 1;
-            a.cm_tiles = c->cm.oseg ? c->cm.oseg_tiles : 0;
-            a.cm_n_orph = c->cm.oseg ? 0 : c->cm.n_orph;
-            a.cm_blocks = c->cm.oseg ? 0 : std::max(1, (int)cdiv(c->cm.n_orph, kBS));
-            c->cm_pending = false;
-        } else if ((rc = flush_commit(c))) {
-            return rc;
-        }
-    }
-    // large one-GPU tables (<= 64 group rows): no k_plan2 -- k_emit2's queue blocks reduce
-    // the group rows, its compaction workgroups the tile counts before theirs
-    if (!a.fused && a.segw && a.grp_on && !c->shard && !c->deque && !c->l_win && c->gp_on && nbf <= 4096 * 4 &&
-        nbw <= 4096 * 4) {
-        a.gp = 1;
-        a.gpcheck = c->gpcheck;
-    }
-    a.cmix = (c->cmix_on && !a.fused && !a.f_emit);
-    // slot tiles per k_scan W-role workgroup: unfused (large) tables 4 -- fewer, longer
-    // workgroups (configs[3]: scan 16.3 -> 14.8 us with 2, tick 55.4 -> 53.4 us with 4)
-    a.wtiles = c->wtiles ? c->wtiles : (a.fused ? 1 : 4);
-    // queue blocks per k_scan Q-role workgroup in the same (4-tile) instance: one-GPU unfused
-    // tables with ride-along queue records
-    a.qtiles = (c->qtiles != 1 && a.wtiles == 4 && !a.fused && !c->shard && !c->deque && a.qaos && a.R <= kRFused)
-                   ? 4
-                   : 1;
-    if (!a.slots_in_scan && !a.slots_in_apply) {
-        Timer t(c, "slots");
-        launch_slots(a, t.st());
-    }
-    {
-        Timer t(c, "scan");
-        launch_scan(a, t.st());
-    }
-    if (a.f_sep) {
-        Timer t(c, "logscan");
-        launch_logscan(a, ls_grid, t.st());
-    }
-    if (!a.fused && (!a.gp || a.gpcheck)) {
-        Timer t(c, "plan");
-        launch_plan(a, t.st());
-    }
-    {
-        Timer t(c, "emit");
-        if (a.segw) launch_emit2(a, t.st());
-        else launch_emit(a, t.st());
-    }
-    if (c->l_cout && head > 0) launch_orph_gather(c->cout_orph, c->orphans, c->fcnt, nbf, Stream(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return FB_OK;
 }
 
 }  // namespace
@@ -1918,9 +1754,8 @@ int fb_exchange_bytes(fb_ctx *c, int32_t n_events, int64_t *bytes) {
                                             xgrows_bytes(c->world, kXGroupR, Qlog)).total});
     } else {
         const int R = c->launched ? c->l_R : kRFused;
-        const bool xoff = !c->xplan_on && xrows_mode(c->world, R, Qlog) == 2;
-        *bytes = (int64_t)xlayout(c->world, E, Qlog, xc_width(R), xoff ? 0 : xrows_bytes(c->world, R, Qlog),
-                                  xgrows_bytes(c->world, R, Qlog)).total;
+        const XRows xr = exchange_rows(c->paths, c->world, R, Qlog);
+        *bytes = (int64_t)xlayout(c->world, E, Qlog, xc_width(R), xr.rows, xr.grows).total;
     }
     return FB_OK;
 }
@@ -2008,7 +1843,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         // a batch already in this GPU's memory (e.g. parsed there, or staged ahead): the
         // tick reads it in place and its first kernel checks it (an invalid message is
         // overwritten with a harmless one and fb_tick_wait names it); no host pass
-        if (!(c->ev_head && c->ev_ll))
+        if (!(c->ev_head && c->paths.ev_ll))
             return fail(c, FB_EINVAL, "device-resident messages need a one-GPU heartbeat context");
         c->st_dev[0] = kind;
         c->st_dev[1] = slot;
@@ -2050,7 +1885,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         // (slots, kinds, timestamps; fb_tick_wait names the first offending event and the
         // tick commits nothing): the host does not read them at all.  The round table is
         // then sized from the last tick's free counts (a wider one is a rerun away).
-        const bool dev_chk = direct && c->ev_head && c->ev_ll;
+        const bool dev_chk = direct && c->ev_head && c->paths.ev_ll;
         auto part = [&](int pi) {
             if (dev_chk) {
                 pbad[pi] = 0;
@@ -2351,11 +2186,11 @@ int fb_tick_wait(fb_ctx *c, fb_tick_result *res) {
         int rc = enqueue_tick(c);
         if (rc) return rc;
     }
-    if (c->fault_qlen >= 0) {
+    if (c->paths.fault_qlen >= 0) {
         // (a window tick reported the injected length from the device already)
-        c->hout->new_qlen = c->fault_qlen;
-        c->hout->win_qlen = c->fault_qlen;
-        c->fault_qlen = -1;
+        c->hout->new_qlen = c->paths.fault_qlen;
+        c->hout->win_qlen = c->paths.fault_qlen;
+        c->paths.fault_qlen = -1;
     }
     if (int rc_ = check_lengths(c)) {
         c->l_eager = false;
@@ -2455,7 +2290,7 @@ int fb_tick_commit(fb_ctx *c) {
         // the device committed the tick right behind it (fb_tick_launch_staged)
     } else if (c->W > 0 || n_orph > 0 || (c->ev_clr && c->l_E > 0)) {
         int grid = 0;
-        const bool defer = c->ev_head && c->ev_ll && !c->l_win;
+        const bool defer = c->ev_head && c->paths.ev_ll && !c->l_win;
         const CommitArgs a = commit_args(c, false, grid);
         if (defer) {  // (by default a window tick's commit runs at once)
             // deferred: the next launch's k_ev_link runs it (or flush_commit)
@@ -2944,31 +2779,15 @@ int fb_set_path(fb_ctx *c, const char *name, int value) {
     if (!c || !name) return FB_EINVAL;
     if (c->launched) return fail(c, FB_ESTATE, "fb_set_path between ticks only");
     if (int rc_ = flush_commit(c)) return rc_;
-    const std::string n(name);
-    if (n == "plan" && value >= 0 && value <= 2) c->force_plan = value;
-    else if (n == "logscan" && value >= -1 && value <= 1) c->logscan = value;
-    else if (n == "split_slots" && value >= -1 && value <= 1) c->split_slots = value;
-    else if (n == "ev_ll" && (value == 0 || value == 1)) c->ev_ll = value;
-    else if (n == "rs_wide" && (value == 0 || value == 1)) c->rs_wide = value;
-    else if (n == "fault_qlen") c->fault_qlen = value;
-    else if (n == "xplan" && (value == 0 || value == 1)) c->xplan_on = value;
-    else if (n == "gp" && (value == 0 || value == 1)) c->gp_on = value;
-    else if (n == "win_direct" && (value == 0 || value == 1)) c->win_direct = value;
-    else if (n == "xself" && (value == 0 || value == 1)) c->xself_on = value;
-    else if (n == "wfirst" && (value == 0 || value == 1)) c->wfirst_on = value;
-    else if (n == "gpcheck" && (value == 0 || value == 1)) c->gpcheck = value;
-    else if (n == "cmix" && (value == 0 || value == 1)) c->cmix_on = value;
-    else if (n == "wtiles" && (value == 0 || value == 1 || value == 2 || value == 4)) c->wtiles = value;
-    else if (n == "qtiles" && (value == 0 || value == 1 || value == 4)) c->qtiles = value;
-    else if (n == "lazy" && (value == 0 || value == 1)) {
-        if (!value && c->stale_any) {  // the entries left so far leave the log first
+    for (const PathKnob &k : kPathKnobs) {
+        if (strcmp(name, k.name) || !knob_allows(k, value)) continue;
+        // "lazy" off: the entries left so far leave the log first
+        if (k.member == &PathKnobs::lazy_on && !value && c->stale_any)
             if (int rc_ = log_settle(c)) return rc_;
-        }
-        c->lazy_on = value;
+        c->paths.*k.member = value;
+        return FB_OK;
     }
-    else if (n == "xcfirst" && (value == 0 || value == 1)) c->xcfirst_on = value;
-    else return fail(c, FB_EINVAL, "fb_set_path(\"%s\", %d): unknown path or value", name, value);
-    return FB_OK;
+    return fail(c, FB_EINVAL, "fb_set_path(\"%s\", %d): unknown path or value", name, value);
 }
 
 int fb_timing_enable(fb_ctx *c, int enable) {

@@ -17,7 +17,8 @@ def build_lib(verbose=False, out=None, defines=()):
     """Compile libfaasbal.so (or a diagnostic variant with extra -D defines)."""
     OUT_ = out or OUT
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "faasbal_kernels.h"), os.path.join(REPO, "include", "faasbal.h")]
+    hdrs = [os.path.join(CSRC, "faasbal_kernels.h"), os.path.join(CSRC, "faasbal_plan.h"),
+            os.path.join(REPO, "include", "faasbal.h")]
     stamp = OUT_ + ".defines"
     want = " ".join(sorted(defines))
     if os.path.exists(OUT_) and os.path.exists(stamp) and open(stamp).read() == want:
