@@ -173,7 +173,6 @@ struct fb_ctx {
     // k_ev_link (extra blocks) or flushed as its own launch by the next call that needs it
     bool cm_pending = false;
     CommitArgs cm{};
-    int cm_grid = 0;
     int eager = 0;             // fb_set_eager_commit: window ticks commit on the device right behind the tick
     bool l_eager = false;      // the launched tick's eager commit is enqueued (until a rerun cancels it)
     PostRec *post = nullptr;       // post-message records {hb, free, epoch} of touched slots
@@ -605,7 +604,7 @@ int flush_commit(fb_ctx *c) {
     c->cm_pending = false;
     HIPCHK(c, hipSetDevice(c->device));
     Timer t(c, "commit");
-    launch_commit(c->cm, c->cm_grid, t.st());
+    launch_commit(c->cm, t.st());
     HIPCHK(c, hipGetLastError());
     return FB_OK;
 }
@@ -773,7 +772,7 @@ EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const
     ea.orph_grp = a.f_emit ? 1 : 0;
     if (p.commit == CommitPlan::in_ev_link) {  // the previous tick's commit rides in this launch
         ea.cm = c->cm;
-        ea.cm_blocks = c->cm_grid;
+        ea.cm_blocks = commit_layout(c->cm).grid();
     }
     // the slot purge (k_scan's W role) runs in k_ev_apply_ll's launch
     ea.nbw = a.nbw;
@@ -786,7 +785,7 @@ EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const
         ea.wpart = c->wpart;
         ea.died_tag = c->died_tag;
         ea.wlb = c->wlb;
-        ea.wlb_n = a.nchB + a.nchF + a.nchW;
+        ea.wlb_n = emit_win_layout(a).grid();
         ea.wticket = c->wticket;
         ea.cw = c->cw;
     }
@@ -900,7 +899,7 @@ void fill_tick_args(const fb_ctx *c, const TickPlan &p, const EvLists &l, TickAr
             // qpre's words, the chunk prefixes and totals in opre's
             a.xpre = reinterpret_cast<uint32_t *>(c->qpre);
             a.xct = reinterpret_cast<uint32_t *>(c->opre);
-            a.xA = a.xct + (size_t)cdiv(a.nbq, kXsBlocks) * 2 * a.R;
+            a.xA = a.xct + (size_t)xscan_layout(a).grid() * 2 * a.R;
             a.xtk = c->xs_tk;
         }
         a.xgrows = p.xgb ? c->xbuf + p.xl.grows : nullptr;
@@ -1016,8 +1015,7 @@ int launch_window_tick(fb_ctx *c, const TickPlan &p, const TickArgs &a, const Ev
             // an eager commit follows: the launch's own completion signal is the event the
             // host waits for (a separate event record between the two kernels cost ~6 us)
             c->tick_ev_set = !c->timing && c->eager && c->reruns == 0;
-            launch_emit_win(a, a.nchB + a.nchF + a.nchW,
-                            c->tick_ev_set ? Stream(c->stream, nullptr, c->tick_ev) : t.st());
+            launch_emit_win(a, c->tick_ev_set ? Stream(c->stream, nullptr, c->tick_ev) : t.st());
         } else if (int rc = launch_common_stage(c, p, a, ea, p.stages[i], ps)) {
             return rc;
         }
@@ -1950,7 +1948,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
     return FB_OK;
 }
 
-static CommitArgs commit_args(fb_ctx *c, bool eager, int &grid);
+static CommitArgs commit_args(fb_ctx *c, bool eager);
 
 int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     if (!c) return FB_EINVAL;
@@ -2019,11 +2017,10 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     if (c->eager && c->l_win) {
         // eager: the window tick's commit right behind it on the stream; it commits only
         // if the tick finished as a window tick (fb_tick_wait reruns it otherwise)
-        int grid = 0;
-        const CommitArgs a = commit_args(c, true, grid);
+        const CommitArgs a = commit_args(c, true);
         if (!c->tick_ev_set) HIPCHK(c, hipEventRecord(c->tick_ev, c->stream));  // fb_tick_wait waits for the tick, not its commit
         Timer t(c, "commit");
-        launch_commit(a, grid, t.st());
+        launch_commit(a, t.st());
         HIPCHK(c, hipGetLastError());
         c->l_eager = true;
     }
@@ -2221,7 +2218,7 @@ int fb_tick_wait(fb_ctx *c, fb_tick_result *res) {
 // The commit of the launched tick.  eager: built at launch, before the tick's results
 // exist -- the window's head and appended positions are read by the kernel from the
 // tick's results, and every orphan tile and appended position gets blocks (grid-stride).
-static CommitArgs commit_args(fb_ctx *c, bool eager, int &grid) {
+static CommitArgs commit_args(fb_ctx *c, bool eager) {
     // lazy clears: the redistributed entries stay in the log (dead to every later tick)
     const bool lazy = lazy_ctx(c);
     const int64_t n_orph = (eager || lazy) ? 0 : c->last.n_orphans_local;
@@ -2276,8 +2273,6 @@ static CommitArgs commit_args(fb_ctx *c, bool eager, int &grid) {
         a.n_tomb = 2 * c->l_E;
         a.post_rf = c->post_rf;
     }
-    grid = a.nbw + a.nbo + (int)cdiv(a.n_clr, kBS) +
-           (a.win ? a.nbap + (int)cdiv(a.n_tomb, kBS) : 0);
     return a;
 }
 
@@ -2289,17 +2284,15 @@ int fb_tick_commit(fb_ctx *c) {
     if (c->l_eager) {
         // the device committed the tick right behind it (fb_tick_launch_staged)
     } else if (c->W > 0 || n_orph > 0 || (c->ev_clr && c->l_E > 0)) {
-        int grid = 0;
         const bool defer = c->ev_head && c->paths.ev_ll && !c->l_win;
-        const CommitArgs a = commit_args(c, false, grid);
+        const CommitArgs a = commit_args(c, false);
         if (defer) {  // (by default a window tick's commit runs at once)
             // deferred: the next launch's k_ev_link runs it (or flush_commit)
             c->cm = a;
-            c->cm_grid = grid;
             c->cm_pending = true;
         } else {
             Timer t(c, "commit");
-            launch_commit(a, grid, t.st());
+            launch_commit(a, t.st());
             HIPCHK(c, hipGetLastError());
         }
     }
@@ -2561,9 +2554,7 @@ int fb_get_outputs_compact(fb_ctx *c, int32_t *slot, uint8_t *cnt, int64_t cap, 
     auto add = [&](void *dst, const void *src, int64_t bytes) -> bool {
         uint32_t *d = (bytes & 3) == 0 ? mapped(dst) : nullptr;
         if (!d) return false;
-        const int b0 = m.n ? m.blk0[m.n - 1] + (int)std::min<int64_t>(
-                                                       std::max<int64_t>(1, (m.words[m.n - 1] + 4 * kBS - 1) / (4 * kBS)), 512)
-                           : 0;
+        const int b0 = m.n ? m.blk0[m.n - 1] + copy_blocks(m.words[m.n - 1]) : 0;
         m.dst[m.n] = d;
         m.src[m.n] = (const uint32_t *)src;
         m.words[m.n] = bytes / 4;

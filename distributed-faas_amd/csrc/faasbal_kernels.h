@@ -7,6 +7,7 @@ namespace fb {
 
 constexpr int kBS = 256;           // threads per workgroup (4 wave64)
 constexpr int kWaves = kBS / 64;
+__host__ __device__ constexpr int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 constexpr int kTrashRows = 1024;   // k_emit2: trash rows (one per block, modulo) for branch-free stores
 constexpr int kStagePar = 16384;   // host: event batches this large are staged by the worker pool
 // sharded exchange record: a rank's orphan count as partials on kXRecLines separate
@@ -448,7 +449,9 @@ struct TickArgs {
 };
 
 
-// Host-side launchers (defined in faasbal_kernels.hip; grid sizes are the caller's).
+// Host-side launchers (defined in faasbal_kernels.hip).  A multi-role kernel's grid and dynamic
+// LDS come from its layout (faasbal_layout.h), a one-role kernel's from its element count;
+// only k_logscan's workgroup count is the plan's (TickPlan::ls_grid).
 // A launch target: the stream, plus optional dispatch-packet timing events
 // (hipExtLaunchKernel records them at the kernel's own start and end, the
 // interval rocprofv3's kernel trace reports).
@@ -497,18 +500,18 @@ void launch_xscan(const TickArgs &a, Stream st);
 void launch_emit(const TickArgs &a, Stream st);
 void launch_emit2(const TickArgs &a, Stream st);
 void launch_emit_shard(const TickArgs &a, Stream st);
-void launch_emit_win(const TickArgs &a, int grid, Stream st);
+void launch_emit_win(const TickArgs &a, Stream st);
 // k_emit_win workgroups resident per CU at once (the occupancy calculator; 0 on failure)
 int emit_win_resident_per_cu();
 void launch_pos_rebuild(int32_t *pos, const int32_t *queue, const int32_t *qfree, int64_t off, int64_t n, Stream st);
 // evicted slots in ascending order from the per-slot status bytes and per-tile counts (two
 // launches: a one-workgroup scan of the tile counts, then one block per tile)
 void launch_evict_gather(int32_t *dst, const uint8_t *st, const uint32_t *wcnt, int64_t *wpre, int W, Stream s);
-void launch_commit(const CommitArgs &a, int grid, Stream st);
+void launch_commit(const CommitArgs &a, Stream st);
 // dst[i] = src[i], i < n (dst may be host memory mapped for the device: stores cross PCIe)
 void launch_copy_words(uint32_t *dst, const uint32_t *src, int64_t n, Stream st);
 // up to 4 word copies in one launch; copy i uses blocks [blk0[i], blk0[i + 1]) (the last:
-// up to the grid's end), the caller sizes blk0
+// copy_blocks of its words), the caller fills blk0 (CopyMultiLayout, faasbal_layout.h)
 struct CopyMulti {
     uint32_t *dst[4];
     const uint32_t *src[4];

@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "faasbal_kernels.h"
+#include "faasbal_layout.h"
 
 namespace fb {
 
@@ -823,10 +823,10 @@ __device__ __forceinline__ void commit_slot(const CommitArgs &a, int s, bool t, 
 // wq_head / napp: the window's new head and appended positions (a.wq_head / a.napp, or
 // read from the tick's results by an eager commit)
 __device__ __forceinline__ void commit_body(const CommitArgs &a, int blk, int64_t wq_head, int64_t napp) {
-    const int nclr = (a.n_clr + kBS - 1) / kBS;
-    if (a.win && blk >= a.nbw + a.nbo + nclr) {
-        const int rb = blk - a.nbw - a.nbo - nclr;
-        if (rb < a.nbap) {
+    const CommitLayout lay = commit_layout(a.nbw, a.nbo, a.n_clr, a.nbap, a.n_tomb);
+    if (a.win && blk >= lay.first(kCmAppended)) {
+        const int rb = lay.rel(kCmAppended, blk);
+        if (rb < lay.n[kCmAppended]) {
             // window tick: the slot at each appended position has its position there
             for (int64_t i = (int64_t)rb * kBS + threadIdx.x; i < napp; i += (int64_t)a.nbap * kBS)
                 a.pos[a.wq_buf[a.wq_tail + i]] = (int32_t)(a.wq_tail + i);
@@ -834,9 +834,8 @@ __device__ __forceinline__ void commit_body(const CommitArgs &a, int blk, int64_
         }
         // the committed positions of queued slots a front / back insertion moved (recorded
         // by k_emit_win per list entry, before any position changed) become tombstones
-        const int ntb = (a.n_tomb + kBS - 1) / kBS;
-        if (rb < a.nbap + ntb) {
-            const int64_t j = (int64_t)(rb - a.nbap) * kBS + threadIdx.x;
+        if (rb < lay.n[kCmAppended] + lay.n[kCmTombs]) {
+            const int64_t j = (int64_t)(rb - lay.n[kCmAppended]) * kBS + threadIdx.x;
             if (j < a.n_tomb) {
                 const int32_t p = a.tomb[j];
                 if (p >= wq_head && p < a.wq_tail) a.wqf[p] = kTomb;
@@ -844,29 +843,29 @@ __device__ __forceinline__ void commit_body(const CommitArgs &a, int blk, int64_
         }
         return;
     }
-    if (blk >= a.nbw + a.nbo) {
+    if (blk >= lay.first(kCmCleared)) {
         // entries the committed tick's results completed (one-GPU heartbeat contexts keep
         // the log read-only during the tick): they leave the in-flight log now
-        const int64_t e = (int64_t)(blk - a.nbw - a.nbo) * kBS + threadIdx.x;
+        const int64_t e = (int64_t)lay.rel(kCmCleared, blk) * kBS + threadIdx.x;
         if (e >= a.n_clr) return;
         const int32_t q = a.ev_clr[e];
         if (q >= 0) a.log_slot[q] = -1;
         return;
     }
-    if (blk >= a.nbw && a.oseg) {
+    if (blk >= lay.first(kCmOrphans) && a.oseg) {
         // orphans in per-tile segments (fused one-GPU and window ticks): a wave per 64 tiles
         // (one count load each), then the tiles that hold orphans one after another
         // a wave per tile: 64 orphans per round (a fused tick leaves ~100 per tile, a
         // window tick ~1; most of a window tick's waves read one count and stop)
-        const int t = (blk - a.nbw) * kWaves + wave_id();
+        const int t = (blk - lay.first(kCmOrphans)) * kWaves + wave_id();
         const uint32_t n = t < a.oseg_tiles ? a.oseg[t] : 0u;
         for (uint32_t i = lane_id(); i < n; i += 64) a.log_slot[a.orphans[(int64_t)t * kFTile + i]] = -1;
         return;
     }
-    if (blk >= a.nbw) {
+    if (blk >= lay.first(kCmOrphans)) {
         // the committed tick redistributed these entries: their tasks now run under new
         // sequence numbers, so the old entries leave the in-flight log
-        const int64_t i = (int64_t)(blk - a.nbw) * kBS + threadIdx.x;
+        const int64_t i = (int64_t)(blk - lay.first(kCmOrphans)) * kBS + threadIdx.x;
         if (i >= a.n_orph) return;
         const int64_t q = a.orphans[i];
         const int64_t li = a.shard ? lseq_find(a.lseq, a.head_local, q) : q;
@@ -908,7 +907,7 @@ __global__ __launch_bounds__(kBS) void k_commit(CommitArgs a) {
 constexpr int kLinkMax = 16;
 __global__ __launch_bounds__(kBS) void k_ev_link(EvArgs a) {
     prefetch_args(a);
-    const int lb = (int)gridDim.x - a.cm_blocks;  // link blocks; the rest commit the previous tick
+    const int lb = ev_link_layout(a, (int)gridDim.x).n[kLinkLink];  // link blocks; the rest commit the previous tick
     if ((int)blockIdx.x >= lb) {
         commit_body(a.cm, (int)blockIdx.x - lb, a.cm.wq_head, a.cm.napp);
         return;
@@ -1089,8 +1088,7 @@ __device__ __forceinline__ void apply_slot_tiles(const EvArgs &a, int blk0) {
 __global__ __launch_bounds__(kBS) void k_ev_apply_ll(EvArgs a) {
     prefetch_args(a);
     APPLY_STAMP(0);
-    const int nwb = a.wtiles == 4 ? (a.nbw + 3) / 4 : a.nbw;
-    const int nba = (int)gridDim.x - nwb;  // apply blocks; the rest purge untouched slots
+    const int nba = ev_apply_ll_layout(a, (int)gridDim.x).n[kApplyMsgs];  // apply blocks; the rest purge untouched slots
     if ((int)blockIdx.x >= nba) {
         if (a.wtiles == 4) apply_slot_tiles<4>(a, 4 * ((int)blockIdx.x - nba));
         else apply_slot_tiles<1>(a, (int)blockIdx.x - nba);
@@ -1679,19 +1677,12 @@ __global__ __launch_bounds__(kBS, (WT == 4 ? 8 : 1)) void k_scan(TickArgs a_) {
     __shared__ int32_t m4[kWaves];
     __shared__ unsigned long long s4[kWaves];
     __shared__ uint32_t wc[kWaves][kBS];
-    const int nbf = (a.shard == 2 || a.f_sep || a.f_emit) ? 0 : a.nbf;  // phase 2 re-derives only the queue counts
-    // Q-role workgroups (a.qtiles queue blocks each in the 4-tile instance)
-    const int nqb = (WT == 4 && a.qtiles == 4) ? (a.nbq + 3) >> 2 : a.nbq;
-    // grid: queue blocks first (the critical path: their loads go out before the log
-    // role's gathers fill the memory queues), then log blocks, then slot blocks.  Sharded
-    // phase 1 (a.wfirst): the log and slot blocks first -- there they are the longer ones
-    // (4-5 us against the queue blocks' 3 at configs[3], N = 8) and nothing waits on the
-    // queue role before the exchange
-    const int nfw = (int)gridDim.x - nqb - (a.cm_fold ? a.cm_blocks : 0);
-    const int bid = !a.wfirst ? (int)blockIdx.x
-                              : ((int)blockIdx.x < nfw ? nqb + (int)blockIdx.x
-                                                       : ((int)blockIdx.x < nfw + nqb ? (int)blockIdx.x - nfw
-                                                                                       : (int)blockIdx.x));
+    // (ScanLayout: queue workgroups -- a.qtiles queue blocks each in the 4-tile instance --,
+    // log tiles, slot workgroups, a folded commit's blocks; a.wfirst's order in the grid)
+    const int nbf = scan_log_wgs(a);
+    const int nqb = scan_queue_wgs(a, WT);
+    const int nfw = scan_logslot_wgs((int)gridDim.x, nqb, scan_commit_wgs(a));
+    const int bid = scan_canon(a.wfirst, nqb, nfw, (int)blockIdx.x);
     const int SO = a.nbw;
     STAMP(a, SO, 0);
     if (bid >= nqb && bid - nqb < nbf) {
@@ -1735,11 +1726,10 @@ __global__ __launch_bounds__(kBS, (WT == 4 ? 8 : 1)) void k_scan(TickArgs a_) {
                 died |= d ? (1u << j) : 0u;
             }
         } else {
-        const int nwords = (a.W + 63) >> 6;
         const unsigned long long *dm = a.dmask;
         if (a.lds_bitmap) {
             // <= 2048 words = 1024 int4: at most 4 loads per thread, all in flight together
-            const int n4 = (nwords + 1) >> 1;
+            const int n4 = scan_bitmap_lds(a.W).n4;
             const uint4 *src = reinterpret_cast<const uint4 *>(a.dmask);
             uint4 t[4];
 #pragma unroll
@@ -1778,10 +1768,10 @@ __global__ __launch_bounds__(kBS, (WT == 4 ? 8 : 1)) void k_scan(TickArgs a_) {
         STAMP(a, SO, 15);
         return;
     }
-    if (a.cm_fold && bid >= (int)gridDim.x - a.cm_blocks) {
+    if (a.cm_fold && bid >= FB_SCAN_FIRST_COMMIT((int)gridDim.x, a)) {
         // ---- the previous tick's orphaned log entries leave the log (its folded commit)
         // (a dense list; per-tile segments are cleared by k_emit2's log workgroup of each tile)
-        const int64_t i = (int64_t)(bid - ((int)gridDim.x - a.cm_blocks)) * kBS + threadIdx.x;
+        const int64_t i = (int64_t)(bid - (FB_SCAN_FIRST_COMMIT((int)gridDim.x, a))) * kBS + threadIdx.x;
         if (i < a.cm_n_orph) a.log_slot[a.orphans[i]] = -1;
         return;
     }
@@ -2124,17 +2114,18 @@ struct WinEl {
 };
 // region of chunk ch: 0 backs, 1 fronts, 2 window; [i0, i1) its element range in the region
 __device__ __forceinline__ int win_region(const TickArgs &a, int ch, int64_t &i0, int64_t &i1) {
-    if (ch < a.nchB) {
+    const EmitWinLayout lay = emit_win_layout(a);
+    if (ch < lay.end(kWinBacks)) {
         i0 = (int64_t)ch * kWinCh;
         i1 = min(i0 + kWinCh, (int64_t)a.E);
         return 0;
     }
-    if (ch < a.nchB + a.nchF) {
-        i0 = (int64_t)(ch - a.nchB) * kWinCh;
+    if (ch < lay.end(kWinFronts)) {
+        i0 = (int64_t)(ch - lay.first(kWinFronts)) * kWinCh;
         i1 = min(i0 + kWinCh, (int64_t)a.E);
         return 1;
     }
-    i0 = a.wq_off + (int64_t)(ch - a.nchB - a.nchF) * kWinCh;
+    i0 = a.wq_off + (int64_t)lay.rel(kWinWindow, ch) * kWinCh;
     i1 = min(i0 + kWinCh, a.wq_tail);
     return 2;
 }
@@ -2208,7 +2199,7 @@ __global__ __launch_bounds__(kLsBS) void k_logscan(TickArgs a) {
         STAMP(a, SO, 15);
         return;
     }
-    const int n4 = (((a.W + 63) >> 6) + 1) >> 1;
+    const int n4 = logscan_bitmap_lds(a.W).n4;
     const uint4 *src = reinterpret_cast<const uint4 *>(a.dmask);
     for (int i0 = 0; i0 < n4; i0 += kLsBS * 8) {
         uint4 t[8];
@@ -2312,7 +2303,8 @@ __global__ __launch_bounds__(kBS) void k_plan(TickArgs a) {
     const int bid = blockIdx.x;
     const int SO = 3 * (a.nbw + a.nbf + a.nbq) + 512;  // diagnostic stamp rows
     STAMP(a, SO, 0);
-    if (bid <= 1) {
+    const PlanLayout lay = plan_layout(a);
+    if (bid < lay.end(kPlanSlotScan)) {
         const unsigned long long tot = bid == 0 ? run_excl_scan(a.fcnt, 1, a.nbf, a.fpre, 1, l4)
                                                 : run_excl_scan(a.wcnt, 1, a.nbw, a.wpre, 1, l4);
         if (threadIdx.x == 0) {
@@ -2325,7 +2317,7 @@ __global__ __launch_bounds__(kBS) void k_plan(TickArgs a) {
         }
         return;
     }
-    if (bid == 2) {
+    if (bid < lay.end(kPlanTotals)) {
         // capacity and max c from the queue blocks (sharded phase 2: of the exchanged
         // c bytes); sharded: every rank's orphan count from the exchange records
         int32_t mx = 0;
@@ -2365,10 +2357,9 @@ __global__ __launch_bounds__(kBS) void k_plan(TickArgs a) {
         return;
     }
     // rows: r < R of all positions, then (sharded) r < R of this rank's positions
-    const int rr = bid - 3;
-    const bool mine = rr >= a.R;
-    const int r = mine ? rr - a.R : rr;
-    if (r >= a.R || (mine && !a.shard)) return;
+    if (bid >= lay.grid()) return;
+    const bool mine = bid >= lay.first(kPlanOwnRows);
+    const int r = mine ? bid - lay.first(kPlanOwnRows) : bid - lay.first(kPlanRows);
     const uint32_t *cnt = mine ? a.ocnt : a.qcnt;
     int64_t *pre = mine ? a.opre : a.qpre;
     const unsigned long long tot = run_excl_scan(cnt + r, (size_t)a.R, a.nbq, pre + r, (size_t)a.R, l4);
@@ -2454,7 +2445,7 @@ __global__ __launch_bounds__(kBS) void k_xscan(TickArgs a) {
     __syncthreads();
     STAMP(a, SO, 4);
     if (t == 0) last = __hip_atomic_fetch_add(a.xtk, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                           (uint32_t)(gridDim.x - 1);
+                           (uint32_t)xscan_layout(a, (int)gridDim.x).n[kXscanChunks] - 1u;
     __syncthreads();
     STAMP(a, SO, 5);
     if (!last) {
@@ -2465,7 +2456,7 @@ __global__ __launch_bounds__(kBS) void k_xscan(TickArgs a) {
     // part's chunks loaded at once (up to 64 in registers), then the parts' offsets
     constexpr int NP = kBS / C;
     const int col = t % C, part = t / C;
-    const int nch = (int)gridDim.x, per = (nch + NP - 1) / NP;
+    const int nch = xscan_layout(a, (int)gridDim.x).n[kXscanChunks], per = (nch + NP - 1) / NP;
     const int c0 = part * per;
     if (per <= 64) {
         uint32_t x[64];
@@ -2555,8 +2546,9 @@ __global__ __launch_bounds__(kBS) void k_plan2(TickArgs a) {
     __shared__ int nr_s;
     const int bid = blockIdx.x;
     const int ng = a.ngrp;
-    if (bid >= ng) {
-        const bool f = bid == ng;
+    const int scan0 = plan2_layout(a).first(kPlan2LogScan);  // the two tile-count scans follow the groups
+    if (bid >= scan0) {
+        const bool f = bid == scan0;
         const unsigned long long tot =
             f ? run_excl_scan(a.fcnt, 1, a.nbf, a.fpre, 1, l4) : run_excl_scan(a.wcnt, 1, a.nbw, a.wpre, 1, l4);
         (void)tot;
@@ -2749,7 +2741,8 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
     const int SO = a.nbw + a.nbf + a.nbq + (a.slots_in_scan ? a.nbw : 0);
     STAMP(a, SO, 0);
     const int lane = lane_id(), w = wave_id();
-    if (bid < a.nbq) {
+    const EmitLayout lay = emit_layout(a);
+    if (bid < lay.end(kEmitQueue)) {
         const int b = bid;
         const int64_t pos = (int64_t)b * kBS + threadIdx.x;
         int32_t raw = INT32_MIN;
@@ -2935,9 +2928,9 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
         STAMP(a, SO, 15);
         return;
     }
-    if (bid < a.nbq + a.nbf) {
+    if (bid < lay.end(kEmitLog)) {
         // ---- orphan compaction, ascending sequence
-        const int b = bid - a.nbq;
+        const int b = bid - lay.first(kEmitLog);
         const uint32_t flags = a.ofl[(size_t)b * kBS + threadIdx.x];
         const int64_t off = a.fpre[b];
         uint32_t tot;
@@ -2951,7 +2944,7 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
         return;
     }
     // ---- evicted compaction, ascending slot
-    const int b = bid - a.nbq - a.nbf;
+    const int b = lay.rel(kEmitSlots, bid);
     const int s = b * kBS + threadIdx.x;
     const uint32_t e = (s < a.W) & ((a.st[min(s, a.W > 0 ? a.W - 1 : 0)] & kStEvicted) != 0);
     const int64_t off = a.wpre[b];
@@ -3016,7 +3009,7 @@ __device__ __forceinline__ void emit_log_tile(const TickArgs &a, int t, unsigned
     }
     // the died bitmap (<= kLdsBitmapSlots bits) into LDS: <= 4 int4 per thread, all in flight
     {
-        const int n4 = ((((a.W + 63) >> 6) + 1) >> 1);
+        const int n4 = emit2_bitmap_lds(a.W).n4;
         const uint4 *src = reinterpret_cast<const uint4 *>(a.dmask);
         uint4 t4[4];
 #pragma unroll
@@ -3333,25 +3326,12 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
     // the other parity's group rows, for the next launch's k_scan atomics
     for (int i = (int)blockIdx.x * kBS + (int)threadIdx.x; i < a.zero_words; i += (int)gridDim.x * kBS)
         a.grp_zero[i] = 0;
-    // grid: queue blocks, then compaction blocks -- log workgroups: 4 tiles each (f_emit:
-    // one tile each), then the slot tiles 4 per workgroup
-    const int nbf4 = a.f_emit ? a.nbf : (a.nbf + 3) >> 2;
-    int bid = blockIdx.x;  // the role index
+    // (Emit2Layout: queue blocks, log workgroups, slot workgroups; a.cmix's order in the grid)
+    const int nbf4 = emit2_log_wgs(a.f_emit, a.nbf);
+    int bid = blockIdx.x;  // the canonical index
     if (a.cmix) {
-        // (fb_set_path("cmix")) the compaction rows of 8 workgroups (one per XCD) spread
-        // evenly among the queue rows, so they run beside the queue blocks' load latency
-        // instead of after them; a queue block keeps its XCD (role index mod 8 = blockIdx mod 8)
-        const int nc = nbf4 + ((a.nbw + 3) >> 2);
-        const int x = (int)blockIdx.x & 7, y = (int)blockIdx.x >> 3;
-        const int nqr = (a.nbq + 7) >> 3, ncr = (nc + 7) >> 3, nr = nqr + ncr;
-        const int cr = (int)((int64_t)y * ncr / nr);
-        if ((int)((int64_t)(y + 1) * ncr / nr) > cr) {
-            if (8 * cr + x >= nc) return;
-            bid = a.nbq + 8 * cr + x;
-        } else {
-            if (8 * (y - cr) + x >= a.nbq) return;
-            bid = 8 * (y - cr) + x;
-        }
+        const int nc = nbf4 + quarter(a.nbw);
+        FB_CMIX_CANON(a.nbq, nc, (int)blockIdx.x, bid, return);  // (padding workgroups exit)
     }
     const int qb0 = 0, cb0 = a.nbq;
     if (bid >= qb0 && bid < qb0 + a.nbq) {
@@ -3590,7 +3570,7 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
         return;
     }
     // ---- compaction roles (emit2_compact)
-    if (a.f_emit && bid >= cb0 && bid < cb0 + a.nbf) {  // f_emit: one log workgroup per tile
+    if (a.f_emit && bid >= cb0 && bid < cb0 + a.nbf) {  // f_emit: one log workgroup per tile (nbf4 = a.nbf)
         extern __shared__ __attribute__((aligned(16))) unsigned long long dynbm[];
         STAMP(a, SO, 0);
         emit_log_tile(a, bid - cb0, dynbm);
@@ -3598,6 +3578,7 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
         return;
     }
     STAMP(a, SO, 0);
+    // (rel, the log workgroups before the slot ones: none left after f_emit's log tiles)
     if (a.f_emit) emit2_compact<PLAN, PM == 2 ? 16 : kPeel>(a, bid - cb0 - a.nbf, 0, red);
     else emit2_compact<PLAN, PM == 2 ? 16 : kPeel>(a, bid - cb0, nbf4, red);
     STAMP(a, SO, 15);
@@ -3918,7 +3899,7 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
     } else if (GRP) {  // the other parity's group rows, for the next launch's k_scan atomics
         for (int i = bid * kBS + (int)threadIdx.x; i < a.zero_words; i += (int)gridDim.x * kBS) a.grp_zero[i] = 0;
     }
-    if (bid < a.nbq) {
+    if (bid < emit_shard_layout(a, 1).end(kShardQueue)) {
         const int b = bid;
         const int R = a.R;
         const int64_t pos = (int64_t)b * kBS + threadIdx.x;
@@ -4457,19 +4438,15 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_xp(TickArgs a) {
     constexpr int R = kXGroupR;
     static_assert(R < 64, "one 64-round chunk");
     const int t = threadIdx.x, lane = lane_id(), w = wave_id();
-    const int nqw = (a.nbq + NSB - 1) / NSB;
-    // the compaction workgroups first in the grid (a.xcfirst): they are short, and behind the
-    // queue workgroups -- more than fit on the device at once -- they started only as the first
-    // queue workgroups left, ~10 us in, and ended the kernel (profiles/r06bb_stamps_shard_*)
-    const int ncw = (int)gridDim.x - nqw;
-    const int bid = !a.xcfirst ? (int)blockIdx.x
-                               : ((int)blockIdx.x < ncw ? nqw + (int)blockIdx.x : (int)blockIdx.x - ncw);
+    // (EmitShardLayout: a.xcfirst's order in the grid; profiles/r06bb_stamps_shard_*)
+    const EmitShardLayout lay = emit_shard_layout(a, NSB, (int)gridDim.x);
+    const int bid = lay.canon((int)blockIdx.x), nqw = lay.n[kShardQueue];
     const int SO = 3 * (a.nbw + a.nbf + a.nbq);  // diagnostic stamp rows (stamps builds)
     STAMP(a, SO, 0);
     // the other parity's exchange records, for the next tick's phase 1
     for (int i = bid * kBS + t; i < a.xz_words; i += (int)gridDim.x * kBS) a.xz[i] = 0ull;
     if (bid >= nqw) {
-        shard_compact(a, a.nbq + (bid - nqw));
+        shard_compact(a, emit_shard_layout(a, 1).first(kShardLog) + (bid - nqw));
         return;
     }
     __shared__ uint32_t swc[NSB][kWaves][R + 1], sowc[NSB][kWaves][R + 1];
@@ -4485,7 +4462,7 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_xp(TickArgs a) {
     // flight per thread -- into its chunks' prefixes and the totals (no ticket, no serial
     // last workgroup in k_xscan)
     __shared__ uint32_t cps[3][4][2 * R];
-    const int nch = (a.nbq + kXsBlocks - 1) / kXsBlocks;
+    const int nch = xscan_layout(a).n[kXscanChunks];
     const int ch0 = min(bid * NSB, a.nbq - 1) / kXsBlocks, ch1 = min(bid * NSB + NSB - 1, a.nbq - 1) / kXsBlocks;
     uint32_t xt = 0, xp0 = 0, xp1 = 0;
     if (a.xself) {
@@ -4722,9 +4699,9 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_xp(TickArgs a) {
 __device__ __forceinline__ void shard_compact(const TickArgs &a, int bid) {
     __shared__ uint32_t cred[kWaves];
     const int lane = lane_id(), w = wave_id();
-    const int nbf4 = (a.nbf + 3) >> 2;
-    const bool frole = bid < a.nbq + nbf4;
-    const int t0 = 4 * (frole ? bid - a.nbq : bid - a.nbq - nbf4);
+    const EmitShardLayout lay = emit_shard_layout(a, 1);  // (bid: the canonical index at one queue block each)
+    const bool frole = bid < lay.end(kShardLog);
+    const int t0 = 4 * (frole ? bid - lay.first(kShardLog) : bid - lay.first(kShardSlots));
     const int t = t0 + w;
     const int ntile = frole ? a.nbf : a.nbw;
     // the tile's offset: k_plan's scan of the tile counts, or (no k_plan: group rows) the
@@ -4782,7 +4759,7 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_wide(TickArgs a) {
     prefetch_args(a);
     const int bid = blockIdx.x;
     const int lane = lane_id(), w = wave_id();
-    if (bid >= a.nbq) {
+    if (bid >= emit_shard_layout(a, 1).end(kShardQueue)) {
         shard_compact(a, bid);
         return;
     }
@@ -4988,19 +4965,19 @@ __global__ __launch_bounds__(kBS) void k_evict_compact(int32_t *__restrict__ dst
 // Several word copies in one launch (a tick's outputs into pinned host memory with one
 // kernel instead of one per array): copy i takes the blocks [b_i, b_{i+1}) of the grid.
 __global__ __launch_bounds__(kBS) void k_copy_multi(CopyMulti m) {
-    const int ob = (int)gridDim.x - m.otiles;  // the last otiles blocks gather orphan segments
+    const CopyMultiLayout lay = copy_multi_layout(m, (int)gridDim.x);
+    const int ob = lay.first(kCopyGather);  // the last otiles blocks gather orphan segments
     if ((int)blockIdx.x >= ob) {
         orph_gather_tile(m.odst, m.osrc, m.ocnt, (int)blockIdx.x - ob);
         return;
     }
-    int i = 0;
-    while (i + 1 < m.n && (int)blockIdx.x >= m.blk0[i + 1]) ++i;
+    const int i = lay.copy_of((int)blockIdx.x);
     uint32_t *__restrict__ dst = m.dst[i];
     const uint32_t *__restrict__ src = m.src[i];
     const int64_t n = m.words[i];
-    const int64_t nb = (int64_t)(i + 1 < m.n ? m.blk0[i + 1] : ob) - m.blk0[i];
+    const int64_t nb = (int64_t)lay.end(i) - lay.first(i);
     const int64_t stride = nb * kBS * 4;
-    for (int64_t q0 = ((int64_t)(blockIdx.x - m.blk0[i]) * kBS + threadIdx.x) * 4; q0 < n; q0 += stride) {
+    for (int64_t q0 = ((int64_t)(blockIdx.x - lay.first(i)) * kBS + threadIdx.x) * 4; q0 < n; q0 += stride) {
         uint32_t v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = src[q0 + k < n ? q0 + k : n - 1];
@@ -5049,7 +5026,6 @@ __global__ __launch_bounds__(kBS) void k_copy_words(uint32_t *__restrict__ dst, 
 
 // ------------------------------------------------------------ launchers
 namespace fb {
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 template <int NB>
 static void rs_pass(const RsPass &p, Stream h, Stream s) {
     hipExtLaunchKernelGGL(k_rs_hist<NB>, dim3(p.nblk), dim3(kBS), 0, h.s, h.e0, h.e1, 0, p.kin, p.n, p.shift, p.db,
@@ -5078,19 +5054,14 @@ void launch_ev_apply(const EvArgs &a, Stream st) {
     hipExtLaunchKernelGGL(k_ev_apply, dim3(cdiv(a.E, kBS)), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_ev_link(const EvArgs &a, Stream st) {
-    const int grid = std::max(1, (int)std::max<int64_t>(cdiv(a.E, kBS), std::min<int64_t>(cdiv(a.tbits_words, kBS), 1024)));
-    hipExtLaunchKernelGGL(k_ev_link, dim3(grid + a.cm_blocks), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+    hipExtLaunchKernelGGL(k_ev_link, dim3(ev_link_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_ev_apply_ll(const EvArgs &a, Stream st) {
-    const int nwb = a.wtiles == 4 ? (a.nbw + 3) / 4 : a.nbw;
-    hipExtLaunchKernelGGL(k_ev_apply_ll, dim3(cdiv(a.E, kBS) + nwb), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+    hipExtLaunchKernelGGL(k_ev_apply_ll, dim3(ev_apply_ll_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_copy_multi(const CopyMulti &m, Stream st) {
     if (m.n <= 0 && m.otiles <= 0) return;
-    const int last = m.n - 1;
-    const int grid = (m.n > 0 ? m.blk0[last] + (int)std::min<int64_t>(std::max<int64_t>(1, (m.words[last] + 4 * kBS - 1) / (4 * kBS)), 512) : 0) +
-                     m.otiles;
-    hipExtLaunchKernelGGL(k_copy_multi, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, m);
+    hipExtLaunchKernelGGL(k_copy_multi, dim3(copy_multi_layout(m).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, m);
 }
 void launch_orph_gather(int64_t *dst, const int64_t *src, const uint32_t *cnt, int ntile, Stream st) {
     if (ntile > 0) hipExtLaunchKernelGGL(k_orph_gather, dim3(ntile), dim3(kBS), 0, st.s, st.e0, st.e1, 0, dst, src, cnt, ntile);
@@ -5164,39 +5135,33 @@ static void launch_scan_t(const TickArgs &a, dim3 g, size_t lds, Stream st) {
     }
 }
 void launch_scan(const TickArgs &a, Stream st) {
-    const size_t lds = (a.lds_bitmap && !a.slots_in_scan) ? (size_t)((a.W + 63) / 64) * 8 : 0;
-    const int nbw = (a.shard == 2 || !a.slots_in_scan || a.slots_in_apply) ? 0 : (a.wtiles > 1 ? (a.nbw + a.wtiles - 1) / a.wtiles : a.nbw);
-    const int nbf = (a.shard == 2 || a.f_sep || a.f_emit) ? 0 : a.nbf;
-    const int wt = nbw ? a.wtiles : 1;
-    const int nqb = (wt == 4 && a.qtiles == 4) ? (a.nbq + 3) / 4 : a.nbq;  // (k_scan's own count)
-    const dim3 g(nbf + nbw + nqb + (a.cm_fold ? a.cm_blocks : 0));
-    if (wt == 4) launch_scan_t<4>(a, g, nbf ? lds : 0, st);
-    else if (wt == 2) launch_scan_t<2>(a, g, nbf ? lds : 0, st);
-    else launch_scan_t<1>(a, g, nbf ? lds : 0, st);
+    const dim3 g(scan_layout(a).grid());
+    const size_t lds = scan_lds_bytes(a);
+    const int wt = scan_wt(a);  // the instance ScanLayout counted for
+    if (wt == 4) launch_scan_t<4>(a, g, lds, st);
+    else if (wt == 2) launch_scan_t<2>(a, g, lds, st);
+    else launch_scan_t<1>(a, g, lds, st);
 }
 void launch_logscan(const TickArgs &a, int grid, Stream st) {
-    const size_t lds = (size_t)(((a.W + 63) / 64 + 1) / 2 + 1) * 16;  // + the spare slot
-    hipExtLaunchKernelGGL(k_logscan, dim3(grid), dim3(kLsBS), lds, st.s, st.e0, st.e1, 0, a);
+    hipExtLaunchKernelGGL(k_logscan, dim3(grid), dim3(kLsBS), logscan_bitmap_lds(a.W).bytes, st.s, st.e0, st.e1, 0, a);
 }
 void launch_plan(const TickArgs &a, Stream st) {
     if (a.grp_on)
-        hipExtLaunchKernelGGL(k_plan2, dim3(a.ngrp + 2), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+        hipExtLaunchKernelGGL(k_plan2, dim3(plan2_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
     else
-        hipExtLaunchKernelGGL(k_plan, dim3(3 + (a.shard ? 2 : 1) * a.R), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+        hipExtLaunchKernelGGL(k_plan, dim3(plan_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_xscan(const TickArgs &a, Stream st) {
-    hipExtLaunchKernelGGL(k_xscan<kXGroupR>, dim3((a.nbq + kXsBlocks - 1) / kXsBlocks), dim3(kBS), 0, st.s, st.e0,
+    hipExtLaunchKernelGGL(k_xscan<kXGroupR>, dim3(xscan_layout(a).grid()), dim3(kBS), 0, st.s, st.e0,
                           st.e1, 0, a);
 }
 void launch_emit(const TickArgs &a, Stream st) {
-    FB_LAUNCH_MODE(k_emit, dim3(a.nbq + a.nbf + a.nbw), 0, st, a);
+    FB_LAUNCH_MODE(k_emit, dim3(emit_layout(a).grid()), 0, st, a);
 }
 template <int PM, int NCH>
 static void launch_emit2_t(const TickArgs &a, Stream st) {
-    const int nc = (a.f_emit ? a.nbf : (a.nbf + 3) / 4) + (a.nbw + 3) / 4;
-    const dim3 g(a.cmix ? 8 * ((a.nbq + 7) / 8 + (nc + 7) / 8) : a.nbq + nc);
-    // f_emit: the log workgroups stage the died bitmap in LDS (rounded to whole int4)
-    const size_t lds = a.f_emit ? (size_t)(((a.W + 63) / 64 + 1) / 2) * 16 : 0;
+    const dim3 g(emit2_layout(a).grid());
+    const size_t lds = emit2_lds_bytes(a);  // f_emit: the log workgroups stage the died bitmap
     switch (tick_mode(a)) {
     case kModeIdle: hipExtLaunchKernelGGL((k_emit2<kModeIdle, PM, NCH>), g, dim3(kBS), lds, st.s, st.e0, st.e1, 0, a); break;
     case kModeEvents: hipExtLaunchKernelGGL((k_emit2<kModeEvents, PM, NCH>), g, dim3(kBS), lds, st.s, st.e0, st.e1, 0, a); break;
@@ -5218,15 +5183,15 @@ void launch_emit2(const TickArgs &a, Stream st) {
 }
 void launch_emit_shard(const TickArgs &a, Stream st) {
     if (a.R > 64 * kRCh - 64) {  // rounds 0 .. L+1 beyond the three register chunks
-        hipExtLaunchKernelGGL(k_emit_shard_wide, dim3(a.nbq + (a.nbf + 3) / 4 + (a.nbw + 3) / 4), dim3(kBS), 0, st.s,
-                              st.e0, st.e1, 0, a);
+        hipExtLaunchKernelGGL(k_emit_shard_wide, dim3(emit_shard_layout(a, 1).grid()), dim3(kBS), 0, st.s, st.e0,
+                              st.e1, 0, a);
         return;
     }
-    const dim3 g(a.nbq + (a.nbf + 3) / 4 + (a.nbw + 3) / 4);
+    const dim3 g(emit_shard_layout(a, 1).grid());
     if (a.xplan) {
-        // two queue blocks per workgroup (k_emit_shard_xp; four measured no faster, r06f_probe_*)
-        const dim3 g2((a.nbq + 1) / 2 + (a.nbf + 3) / 4 + (a.nbw + 3) / 4);
-        hipExtLaunchKernelGGL(k_emit_shard_xp<2>, g2, dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+        // kXpBlocks queue blocks per workgroup (r06f_probe_*)
+        const dim3 g2(emit_shard_layout(a, kXpBlocks).grid());
+        hipExtLaunchKernelGGL(k_emit_shard_xp<kXpBlocks>, g2, dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
         return;
     }
     if (a.xrows)
@@ -5247,10 +5212,10 @@ void launch_pos_rebuild(int32_t *pos, const int32_t *queue, const int32_t *qfree
         hipExtLaunchKernelGGL(k_pos_rebuild, dim3(cdiv(n, kBS)), dim3(kBS), 0, st.s, st.e0, st.e1, 0, pos, queue, qfree,
                               off, n);
 }
-void launch_emit_win(const TickArgs &a, int grid, Stream st) {
-    hipExtLaunchKernelGGL(k_emit_win, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+void launch_emit_win(const TickArgs &a, Stream st) {
+    hipExtLaunchKernelGGL(k_emit_win, dim3(emit_win_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
-void launch_commit(const CommitArgs &a, int grid, Stream st) {
-    hipExtLaunchKernelGGL(k_commit, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+void launch_commit(const CommitArgs &a, Stream st) {
+    hipExtLaunchKernelGGL(k_commit, dim3(commit_layout(a).grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 }  // namespace fb

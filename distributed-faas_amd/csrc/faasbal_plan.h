@@ -11,11 +11,9 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "faasbal_kernels.h"
+#include "faasbal_layout.h"
 
 namespace fb {
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------------------
 // fb_set_path: the launch sequences of other table sizes on small (oracle-checkable) inputs
@@ -162,7 +160,7 @@ inline bool plan_window(const WindowIn &w, int &nchW) {
     if (w.mode < 0 && scan * 2 > w.Qn) return false;  // auto: only when most of the queue stays put
     const int n = (int)cdiv(scan, kWinCh);
     if (n == 0) return false;
-    if ((size_t)((w.W + 63) / 64 + 2) * 8 > (size_t)w.max_lds) return false;  // k_logscan's bitmap in LDS
+    if (logscan_bitmap_lds(w.W).bytes > (size_t)w.max_lds) return false;  // k_logscan's bitmap in LDS
     const int nchB = (int)cdiv(w.E, kWinCh);
     if (2 * nchB + n > kWinMaxCh) return false;
     // room for the appends (backs, served workers with c > 1) behind the window
@@ -305,17 +303,15 @@ inline void plan_tick(const PlanIn &in, TickArgs &a, TickPlan &p) {
     a.slots_in_scan = (k.split_slots > 0 || (k.split_slots < 0 && W > kLdsBitmapSlots)) ? 0 : 1;
     // ... or better, while the bitmap fits in one workgroup's LDS: the W-role of
     // k_scan writes it and k_logscan tests every entry against an LDS copy
-    const size_t bm_bytes = (size_t)(((W + 63) / 64 + 1) / 2 + 1) * 16;
     a.f_sep = (head > 0 && !in.deque && (k.logscan > 0 || (k.logscan < 0 && W > kLdsBitmapSlots)) &&
-               bm_bytes <= (size_t)in.max_lds && !(in.shard && in.phase == 2)) ? 1 : 0;
+               logscan_bitmap_lds(W).bytes <= (size_t)in.max_lds && !(in.shard && in.phase == 2)) ? 1 : 0;
     if (a.f_sep) a.slots_in_scan = 1;
     // fused one-GPU ticks: O from the slot purge's in-flight counts, the orphans flagged
     // and compacted by k_emit2's log workgroups (k_scan without log blocks); not when the
     // log role was asked to run as k_logscan (fb_set_path("logscan", 1))
-    const int nbfe = (int)cdiv(nbf, 4);
-    const size_t bm16 = (size_t)(((W + 63) / 64 + 1) / 2) * 16;
+    const int nbfe = quarter(nbf);
     a.f_emit = (in.heartbeat && a.fused && !a.f_sep && W <= kLdsBitmapSlots && nbfe <= kFEmitMaxBlocks &&
-                bm16 <= (size_t)in.max_lds && !in.l_win) ? 1 : 0;
+                emit2_bitmap_lds(W).bytes <= (size_t)in.max_lds && !in.l_win) ? 1 : 0;
     // f_emit and window ticks leave their orphans in per-tile segments
     p.l_oseg = a.f_emit != 0 || in.l_win;
     p.ls_grid = std::max(1, std::min(in.ncu, (int)cdiv(nbf, kLsBS / 64)));
@@ -381,7 +377,7 @@ inline void plan_tick(const PlanIn &in, TickArgs &a, TickPlan &p) {
         a.nchB = (int)cdiv(E, kWinCh);
         a.nchF = a.nchB;
         a.nchW = in.l_nchW;
-        const int nch = a.nchB + a.nchF + a.nchW;
+        const int nch = emit_win_layout(a).grid();
         // few enough chunks to be resident together: chunk = workgroup index, no ticket round
         // before the element loads.  A chunk's look-back waits on lower chunks only, so the
         // direct form needs every lower-indexed workgroup resident or done -- guaranteed while
@@ -407,7 +403,8 @@ inline void plan_tick(const PlanIn &in, TickArgs &a, TickPlan &p) {
         a.xself = (a.xplan && k.xself_on && cdiv(Qlog, kBS) <= 64 * kXsBlocks) ? 1 : 0;
         // k_emit_shard_xp's compaction workgroups first when they are many (configs[3], N = 2:
         // 975 beside 1 774 queue workgroups, emit 30.3 -> 26.9 us; N = 8: 244, no gain)
-        a.xcfirst = (a.xplan && k.xcfirst_on && 4 * ((a.nbf + 3) / 4 + (a.nbw + 3) / 4) > (nbq + 1) / 2) ? 1 : 0;
+        const EmitShardLayout xp = emit_shard_layout(a, kXpBlocks);
+        a.xcfirst = (a.xplan && k.xcfirst_on && 4 * (xp.n[kShardLog] + xp.n[kShardSlots]) > xp.n[kShardQueue]) ? 1 : 0;
         if (a.shard == 1) {
             // phase 1: own slots' purge, orphan flags and free counts into the exchange buffer
             p.kind = TickKind::shard_phase1;

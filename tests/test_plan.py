@@ -7,6 +7,12 @@ the plan of each request.
    kernels_us_per_tick), recorded from the library before plan_tick existed.
 3. fb_exchange_bytes' rows helper and plan_tick's layout agree across the xrows_mode
    boundaries.
+4. Every multi-role kernel's layout (csrc/faasbal_layout.h: what the launcher sizes the grid
+   with and the kernel decodes blockIdx.x with) covers its roles exactly: workgroups
+   0 .. grid-1 give every (role, index) once, the rest padding -- for every launch of 1. and
+   2. and for sweeps around the places where the arithmetic can go wrong.  The dynamic LDS
+   a plan requests fits the device's, and plan_window answers as it did when it tested its
+   own spelling of k_logscan's bitmap size.
 """
 import collections
 import os
@@ -130,3 +136,224 @@ def test_exchange_layout_agrees(probe):
         assert int(a["mode"]) == mode, g
         rows = mode == 1 or (mode == 2 and g["xplan"])
         assert (int(a["rows"]) > 0) == rows and (int(a["grows"]) > 0) == (mode == 1 and g["R"] == 32), g
+
+
+# ------------------------------------------------------------------ 4. grids and LDS
+def _kernels(ans):
+    """{kernel: {grid, n, pad, cover, ...}} of a layout / walk answer."""
+    out = collections.defaultdict(dict)
+    for k, v in ans.items():
+        if "." in k:
+            out[k.split(".")[0]][k.split(".")[1]] = v
+    return dict(out)
+
+
+def _check_cover(ans, where, pad_ok=()):
+    ks = _kernels(ans)
+    for name, k in ks.items():
+        if "cover" not in k:
+            continue  # (k_logscan: one role, its grid is the plan's)
+        n = [int(x) for x in k["n"].split(",")]
+        assert k["cover"] == "1", (where, name, k)
+        assert int(k["grid"]) == sum(n) + int(k["pad"]) and min(n) >= 0, (where, name, k)
+        assert int(k["pad"]) == 0 or name in pad_ok, (where, name, k)
+    return ks
+
+
+# the kernel(s) each stage of a plan launches through a layout
+def _expected_kernels(a):
+    st = _stages(a)
+    want = []
+    for s in st:
+        if s == "ev_link":
+            want += ["k_ev_link"] + (["k_commit"] if a["commit"] == "2" else [])
+        elif s == "ev_apply" and a["grouping"] == "1":
+            want.append("k_ev_apply_ll")
+        elif s == "scan":
+            want.append("k_scan")
+        elif s == "scan2":
+            want.append("k_scan2")
+        elif s == "commit":
+            want.append("k_commit")
+        elif s == "plan":
+            want.append("k_xscan" if a["xplan"] == "1" else "k_plan2" if a["grp_on"] == "1" else "k_plan")
+        elif s == "emit":
+            want.append({"0": "k_emit_win", "2": "k_emit_shard"}.get(a["kind"], "k_emit2" if a["segw"] == "1" else "k_emit"))
+    return want
+
+
+def _layout_fields(f):
+    """A launch's PlanIn fields plus the pending commit's CommitArgs as fb_tick_commit builds them."""
+    f = dict(f)
+    if f.get("cm_pending"):
+        f.update({"cm.nbw": -(-f["W"] // 256), "cm.nbo": -(-f.get("cm_n_orph", 0) // 256), "cm.n_clr": f.get("cm_n_clr", 0)})
+    f["tbits"] = 0 if f.get("shard") or f.get("deque") else 1
+    return f
+
+
+def _check_plan_layouts(probe, fields, where):
+    a = probe([("layout", _layout_fields(fields))])[0]
+    ks = _check_cover(a, where, pad_ok=("k_emit2",))
+    walked = [k for k in ks if "cover" in ks[k]]
+    assert sorted(walked) == sorted(set(_expected_kernels(a))), (where, walked, _stages(a))
+    for k in ks.values():  # every dynamic-LDS request fits
+        assert int(k.get("lds", 0)) <= fields["max_lds"], (where, k)
+    if a["f_sep"] == "1" or a["kind"] == "0":
+        assert "logscan" not in _stages(a) or "lds" in ks["k_logscan"], where
+    return a, ks
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in pc.CASES])
+def test_layouts_cover_table(probe, name):
+    for i, (fields, _) in enumerate(pc.case_launches(pc.BY_NAME[name], _window(probe))):
+        if fields is not None:
+            _check_plan_layouts(probe, fields, (name, i))
+
+
+def test_layouts_cover_workloads(probe):
+    for name, launches, _ in pc.workloads(_window(probe)):
+        for i, f in enumerate(launches):
+            _check_plan_layouts(probe, f, (name, i))
+
+
+def _walk(probe, kernel, grid):
+    reqs = [dict(g) for g in grid]
+    lines = ["walk kernel=%s" % kernel + "".join(" %s=%d" % kv for kv in g.items()) for g in reqs]
+    return list(zip(reqs, probe(lines)))
+
+
+def test_cmix_and_emit2_sweep(probe):
+    """k_emit2: queue blocks 1..40 x compaction workgroups 0..40 under cmix (whole rows of 8,
+    the tails padding) and without; tile counts at 4k-1, 4k, 4k+1; f_emit's one-tile log role."""
+    grid = [dict(nbq=q, nbf=4 * (nc // 2), nbw=4 * (nc - nc // 2), cmix=cm) for q in range(1, 41) for nc in range(41)
+            for cm in (0, 1)]
+    grid += [dict(nbq=q, nbf=f, nbw=w, cmix=cm, f_emit=fe) for q in (1, 8, 9) for f in (0, 3, 4, 5, 7, 8, 9)
+             for w in (1, 3, 4, 5, 7, 8, 9) for cm in (0, 1) for fe in (0, 1)]
+    for g, a in _walk(probe, "k_emit2", grid):
+        k = _check_cover(a, g, pad_ok=("k_emit2",))["k_emit2"]
+        nf = g["nbf"] if g.get("f_emit") else -(-g["nbf"] // 4)
+        assert k["n"] == "%d,%d,%d" % (g["nbq"], nf, -(-g["nbw"] // 4)), g
+        nc = nf + -(-g["nbw"] // 4)
+        assert int(k["grid"]) == (8 * (-(-g["nbq"] // 8) + -(-nc // 8)) if g["cmix"] else g["nbq"] + nc), g
+        assert g["cmix"] or k["pad"] == "0", g
+
+
+def test_scan_sweep(probe):
+    """k_scan: wfirst's permutation (queue blocks 1..39 x log + slot workgroups 0..39, with and
+    without a folded commit's blocks); wtiles x qtiles x slot workgroups present or absent --
+    without them the one-tile instance runs and qtiles groups nothing."""
+    grid = [dict(nbq=q, nbf=x // 2, nbw=x - x // 2, wfirst=wf, shard=1, slots_in_scan=1, wtiles=1, cm_fold=cf, cm_blocks=3)
+            for q in range(1, 40) for x in range(40) for wf in (0, 1) for cf in (0, 1)]
+    for g, a in _walk(probe, "k_scan", grid):
+        k = _check_cover(a, g)["k_scan"]
+        assert k["n"] == "%d,%d,%d,%d" % (g["nbq"], g["nbf"], g["nbw"], 3 * g["cm_fold"]), g
+        assert not g["cm_fold"] or int(k["commit0"]) == g["nbq"] + g["nbf"] + g["nbw"], g
+    grid = [dict(nbq=q, nbf=f, nbw=w, wtiles=wt, qtiles=qt, slots_in_scan=sl, f_emit=fe, cm_fold=cf, cm_blocks=2)
+            for q in (1, 3, 4, 5, 8, 9) for f in (0, 5) for w in (1, 3, 4, 5, 7, 8, 9) for wt in (1, 2, 4) for qt in (1, 4)
+            for sl in (0, 1) for fe in (0, 1) for cf in (0, 1)]
+    for g, a in _walk(probe, "k_scan", grid):
+        k = _check_cover(a, g)["k_scan"]
+        nw = -(-g["nbw"] // g["wtiles"]) if g["slots_in_scan"] else 0
+        wt = g["wtiles"] if nw else 1
+        nq = -(-g["nbq"] // 4) if (wt == 4 and g["qtiles"] == 4) else g["nbq"]
+        assert (k["wt"], k["n"]) == (str(wt), "%d,%d,%d,%d" % (nq, 0 if g["f_emit"] else g["nbf"], nw, 2 * g["cm_fold"])), g
+    # phase 2 (scan2): queue workgroups only
+    for g, a in _walk(probe, "k_scan", [dict(nbq=7, nbf=5, nbw=9, shard=2, slots_in_scan=1, wtiles=4, qtiles=4)]):
+        assert _check_cover(a, g)["k_scan"]["n"] == "7,0,0,0"
+
+
+def test_emit_shard_sweep(probe):
+    """k_emit_shard / _wide (a queue block per workgroup) and k_emit_shard_xp (two), xcfirst on
+    and off, queue blocks odd and even, tile counts around multiples of 4."""
+    grid = [dict(nbq=q, nbf=f, nbw=w, nsb=nsb, xcfirst=xc) for q in (1, 2, 7, 8, 39, 40) for f in (0, 3, 4, 5, 8, 9)
+            for w in (1, 3, 4, 5, 8, 9) for nsb in (1, 2) for xc in (0, 1)]
+    for g, a in _walk(probe, "k_emit_shard", grid):
+        k = _check_cover(a, g)["k_emit_shard"]
+        assert k["n"] == "%d,%d,%d" % (-(-g["nbq"] // g["nsb"]), -(-g["nbf"] // 4), -(-g["nbw"] // 4)), g
+
+
+def test_message_and_commit_grids(probe):
+    """k_ev_apply_ll with E at 1, 256, 257; k_ev_link with and without commit blocks; the
+    commit's five ranges empty and non-empty (window ranges only on window commits; an eager
+    commit differs in nbap alone); k_copy_multi's copies and orphan tiles."""
+    grid = [{"ev.E": E, "ev.nbw": w, "ev.wtiles": wt} for E in (1, 256, 257) for w in (1, 3, 4, 5, 1024) for wt in (1, 2, 4)]
+    for g, a in _walk(probe, "k_ev_apply_ll", grid):
+        k = _check_cover(a, g)["k_ev_apply_ll"]
+        assert k["n"] == "%d,%d" % (-(-g["ev.E"] // 256), -(-g["ev.nbw"] // 4) if g["ev.wtiles"] == 4 else g["ev.nbw"]), g
+    grid = [{"ev.E": E, "ev.tbits_words": tb, "ev.cm_blocks": cm} for E in (1, 256, 257, 70000) for tb in (0, 128, 1 << 20)
+            for cm in (0, 1, 17)]
+    for g, a in _walk(probe, "k_ev_link", grid):
+        k = _check_cover(a, g)["k_ev_link"]
+        link = max(1, -(-g["ev.E"] // 256), min(-(-g["ev.tbits_words"] // 256), 1024))
+        assert k["n"] == "%d,%d" % (link, g["ev.cm_blocks"]), g
+    grid = [{"cm.nbw": s, "cm.nbo": o, "cm.n_clr": c, "cm.win": w, "cm.nbap": ap * w, "cm.n_tomb": tb * w}
+            for s in (0, 5) for o in (0, 3) for c in (0, 1, 256, 257) for w in (0, 1) for ap in (0, 1, 1024)
+            for tb in (-1, 0, 1, 512, 513)]
+    for g, a in _walk(probe, "k_commit", grid):
+        k = _check_cover(a, g)["k_commit"]
+        tb = max(0, -(-g["cm.n_tomb"] // 256))
+        assert k["n"] == "%d,%d,%d,%d,%d" % (g["cm.nbw"], g["cm.nbo"], -(-g["cm.n_clr"] // 256), g["cm.nbap"], tb), g
+    grid = [{"copy.n": n, "copy.words0": w0, "copy.words1": 10, "copy.words2": 1024 * 513, "copy.words3": 1, "copy.otiles": ot}
+            for n in range(5) for w0 in (1, 1024, 1025, 1 << 22) for ot in (0, 3)]
+    for g, a in _walk(probe, "k_copy_multi", grid):
+        k = _check_cover(a, g)["k_copy_multi"]
+        blocks = [min(max(1, -(-w // 1024)), 512) for w in (g["copy.words0"], 10, 1024 * 513, 1)]
+        assert k["n"] == ",".join(str(b) for b in blocks[:g["copy.n"]] + [0] * (4 - g["copy.n"]) + [g["copy.otiles"]]), g
+
+
+def test_small_grids(probe):
+    """k_emit, k_plan, k_plan2, k_xscan, k_emit_win: the counts the launchers used to spell out."""
+    for g, a in _walk(probe, "k_emit", [dict(nbq=q, nbf=f, nbw=w) for q in (1, 5) for f in (0, 7) for w in (1, 4)]):
+        assert _check_cover(a, g)["k_emit"]["n"] == "%d,%d,%d" % (g["nbq"], g["nbf"], g["nbw"])
+    for g, a in _walk(probe, "k_plan", [dict(R=R, shard=sh) for R in (32, 256, 4096) for sh in (0, 2)]):
+        assert _check_cover(a, g)["k_plan"]["grid"] == str(3 + (2 if g["shard"] else 1) * g["R"])
+    for g, a in _walk(probe, "k_plan2", [dict(ngrp=n) for n in (1, 2, 64)]):
+        assert _check_cover(a, g)["k_plan2"]["grid"] == str(g["ngrp"] + 2)
+    for g, a in _walk(probe, "k_xscan", [dict(nbq=n) for n in (1, 64, 65, 3547)]):
+        assert _check_cover(a, g)["k_xscan"]["grid"] == str(-(-g["nbq"] // 64))
+    for g, a in _walk(probe, "k_emit_win", [dict(nchB=b, nchF=b, nchW=w) for b in (1, 76) for w in (1, 100)]):
+        assert _check_cover(a, g)["k_emit_win"]["grid"] == str(2 * g["nchB"] + g["nchW"])
+
+
+# plan_window's answers to WINDOW_SWEEP's (W, max_lds), from the probe built at the commit before
+# the layouts: it tested ((W + 63) / 64 + 2) * 8 against max_lds, a spelling of k_logscan's
+# request that is 8 bytes short for an odd word count -- the same answer wherever max_lds is a
+# multiple of 16.  W: small, either side of kLdsBitmapSlots, of a 64 KB and of the 160 KB limit.
+WINDOW_W = [1, 63, 64, 65, 127, 128, (1 << 17) - 1, 1 << 17, (1 << 17) + 1,
+            524096, 524097, 524159, 524160, 524161, 524224, 524225,
+            1310464, 1310465, 1310528, 1310529, 1310591, 1310592, 1310593, 1310656, 1310657]
+WINDOW_YES = {65536: 524160, 160 * 1024: 1310592}   # max_lds: the largest W with the answer yes
+# Where the two spellings differ -- an odd word count and max_lds = 8 mod 16, which no device
+# reports (LDS sizes are multiples of 16) -- plan_window now says no where it said yes: the
+# launch it plans would ask for 8 bytes more than max_lds.  (W, max_lds, answer at the commit
+# before the layouts, answer now); the even word counts beside it answer as before.
+WINDOW_ODD = [(64 * 4093, 32760, 1, 0), (64 * 4092, 32760, 1, 1), (64 * 4094, 32760, 0, 0),
+              (64 * 4093, 32752, 0, 0), (64 * 4093, 32768, 1, 1)]
+
+
+def _logscan_bytes(W):
+    return ((-(-W // 64) + 1) // 2 + 1) * 16
+
+
+def test_window_and_lds_limits(probe):
+    win = _window(probe)
+    for W, max_lds, before, now in WINDOW_ODD:
+        yes, _ = win(dict(win_cap=1, mode=1, lists=1, ev_ll=1, E=64, W=W, max_lds=max_lds, last_L=0, T=100, last_O=0,
+                          win_slack=8192, Qn=W, qoff=0, qcap=4 * W + 100000))
+        assert yes == bool(now) == (_logscan_bytes(W) <= max_lds), (W, max_lds)
+        assert before == int((-(-W // 64) + 2) * 8 <= max_lds), (W, max_lds)  # the old spelling
+    for max_lds, w_yes in WINDOW_YES.items():
+        for W in WINDOW_W:
+            yes, _ = win(dict(win_cap=1, mode=1, lists=1, ev_ll=1, E=64, W=W, max_lds=max_lds, last_L=0, T=100, last_O=0,
+                              win_slack=8192, Qn=W, qoff=0, qcap=4 * W + 100000))
+            assert yes == (W <= w_yes), (W, max_lds)
+            assert yes == (_logscan_bytes(W) <= max_lds), (W, max_lds)
+            # the plans of this table size: whatever they request fits
+            base = dict(pc.DEVICE, max_lds=max_lds, W=W, W_global=W, R=32, head=5000, Qn=W, T=100, lists=1, qaos=1,
+                        heartbeat=int(W <= pc.LDS_BITMAP_SLOTS))
+            for more in (dict(), {"knob.logscan": 1}, dict(E=64), dict(E=64, l_win=int(yes), l_nchW=1)):
+                a, ks = _check_plan_layouts(probe, dict(base, **more), (W, max_lds, more))
+                if a["f_sep"] == "1" or a["kind"] == "0":
+                    assert int(ks["k_logscan"]["lds"]) == _logscan_bytes(W) <= max_lds
+                if a["f_emit"] == "1":
+                    assert int(ks["k_emit2"]["lds"]) == _logscan_bytes(W) - 16 <= max_lds
