@@ -622,7 +622,10 @@ int log_settle(fb_ctx *c) {
     if (!c->stale_any) return FB_OK;
     if (int rc_ = flush_commit(c)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
-    launch_log_normalize(c->log_slot, c->head, c->reg, c->epoch, Stream(c->stream, nullptr, nullptr));
+    if (c->head > 0) {  // (an empty log launches nothing: no events to time)
+        Timer t(c, "settle");
+        launch_log_normalize(c->log_slot, c->head, c->reg, c->epoch, t.st());
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     c->stale_any = false;

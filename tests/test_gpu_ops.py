@@ -34,6 +34,7 @@ def _state_eq(g, o):
     np.testing.assert_array_equal(sg["reg"], so["reg"])
     np.testing.assert_array_equal(sg["free"][reg], so["free"][reg])
     np.testing.assert_array_equal(sg["hb"][reg], so["hb"][reg])
+    np.testing.assert_array_equal(sg["epoch"][reg], so["epoch"][reg])
     np.testing.assert_array_equal(sg["queue"], so["queue"])
     np.testing.assert_array_equal(sg["log"], so["log"])
 

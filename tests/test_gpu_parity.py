@@ -44,6 +44,7 @@ def _cmp_state(g, o, t):
     reg = so["reg"].astype(bool)
     np.testing.assert_array_equal(sg["free"][reg], so["free"][reg], err_msg="tick %d free" % t)
     np.testing.assert_array_equal(sg["hb"][reg], so["hb"][reg], err_msg="tick %d hb" % t)
+    np.testing.assert_array_equal(sg["epoch"][reg], so["epoch"][reg], err_msg="tick %d epoch" % t)
     np.testing.assert_array_equal(sg["queue"], so["queue"], err_msg="tick %d queue" % t)
     np.testing.assert_array_equal(sg["log"], so["log"], err_msg="tick %d log" % t)
     # the per-slot in-flight counts (O of the fused tick) equal the log's live entries

@@ -43,6 +43,7 @@ def _cmp(g, o, a, b, t):
     reg = so["reg"].astype(bool)
     np.testing.assert_array_equal(sg["free"][reg], so["free"][reg], err_msg="tick %d free" % t)
     np.testing.assert_array_equal(sg["hb"][reg], so["hb"][reg], err_msg="tick %d hb" % t)
+    np.testing.assert_array_equal(sg["epoch"][reg], so["epoch"][reg], err_msg="tick %d epoch" % t)
 
 
 @pytest.mark.parametrize("window", [1, 0])

@@ -87,6 +87,7 @@ def _cmp(bals, o, a, b, t):
         m = reg[lo:hi]
         np.testing.assert_array_equal(sg["free"][m], so["free"][lo:hi][m], err_msg="tick %d free" % t)
         np.testing.assert_array_equal(sg["hb"][m], so["hb"][lo:hi][m], err_msg="tick %d hb" % t)
+        np.testing.assert_array_equal(sg["epoch"][m], so["epoch"][lo:hi][m], err_msg="tick %d epoch" % t)
         np.testing.assert_array_equal(sg["queue"], so["queue"], err_msg="tick %d queue" % t)
         assert sg["head"] == len(so["log"])
         glog[sg["log_seq"]] = sg["log"]
