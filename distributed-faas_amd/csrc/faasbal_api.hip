@@ -287,6 +287,9 @@ struct fb_ctx {
     uint32_t *xg_acc = nullptr, *xg_tk = nullptr, *ogrp = nullptr;  // exchanged group rows (phase 1 -> 2)
     uint32_t *xs_tk = nullptr;                        // k_xscan's ticket
     bool stale_any = false;                           // lazy clears: entries of dead registrations may be in the log
+    bool l_enospc = false;                            // the launched tick's wait failed with FB_ENOSPC (log full)
+    void *lc_mem = nullptr;                           // fb_log_compact's scratch (lc_plan's regions; made on first use)
+    size_t lc_cap = 0;
     int full_assign = 0;                              // fb_set_full_assign: phase 2 writes the whole task -> slot array
     bool l_full = false;                              // ... and the last launch did
     int32_t *assign_all = nullptr;                    // (its own allocation, grown as ticks need)
@@ -1428,6 +1431,7 @@ int fb_destroy(fb_ctx *c) {
     if (c->oA_owned) hipFree(c->oA);
     if (c->assign_all) hipFree(c->assign_all);
     if (c->win_owned) hipFree(c->win_mem);
+    if (c->lc_mem) hipFree(c->lc_mem);
     if (c->dbg) hipFree(c->dbg);
     if (c->arena) hipFree(c->arena);
     if (c->hout) hipHostFree(c->hout);
@@ -1708,6 +1712,88 @@ int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {
     HIPCHK(c, hipMemcpy(fq.data(), c->free_[c->cur], W * sizeof(int2), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(reg.data(), c->reg, W, hipMemcpyDeviceToHost));
     for (size_t s = 0; s < W; ++s) inflight[s] = reg[s] ? (uint32_t)bud[s] - (uint32_t)fq[s].x : 0u;
+    return FB_OK;
+}
+
+// The log renumbered densely on the device: count first
+// (k_lc_flag, k_lc_scan write only the scratch), synchronise, check, and only then move.
+int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept) {
+    if (!c) return FB_EINVAL;
+    if (c->shard)
+        return fail(c, FB_ESTATE, "fb_log_compact on a sharded context: its sequence numbers are global across ranks");
+    if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
+    if (c->staged) return fail(c, FB_ESTATE, "fb_log_compact with staged events pending: their sequences would go stale");
+    if (c->launched && c->waited)
+        return fail(c, FB_ESTATE, "fb_log_compact between a tick's wait and its commit: fb_tick_commit first");
+    // (a tick whose wait failed with FB_ENOSPC read only committed state: it is discarded below,
+    // as fb_load_state discards it; a window tick's launch moved the window, which this cannot undo)
+    if (c->launched && (!c->l_enospc || c->l_win))
+        return fail(c, FB_ESTATE, "fb_log_compact with a tick launched: fb_tick_wait and fb_tick_commit first");
+    if (int rc_ = flush_commit(c)) return rc_;
+    HIPCHK(c, hipSetDevice(c->device));
+    const LcPlan p = lc_plan(c->head, c->W, kept_seq != nullptr);
+    if (p.bytes > c->lc_cap) {
+        // sized for this log, doubling, never beyond a full one
+        const size_t full = lc_plan(c->log_cap, c->W_cap, true).bytes;
+        const size_t want = std::max(p.bytes, std::min(2 * c->lc_cap, full));
+        HIPCHK(c, stream_wait(c));
+        void *m = nullptr;
+        const hipError_t e = hipMalloc(&m, want);
+        if (e != hipSuccess)
+            return fail(c, FB_ENOMEM, "hipMalloc(compaction scratch %zu B) failed: %s", want, hipGetErrorString(e));
+        if (c->lc_mem) hipFree(c->lc_mem);
+        c->lc_mem = m;
+        c->lc_cap = want;
+    }
+    char *const base = (char *)c->lc_mem;
+    LcArgs a{};
+    a.log = c->log_slot;
+    a.head = c->head;
+    a.W = c->W;
+    a.nt = p.nt;
+    a.live_chk = c->stale_any ? 1 : 0;
+    a.reg = c->reg;
+    a.epoch = c->epoch;
+    a.bitmap = (unsigned long long *)(base + p.bitmap);
+    a.wrel = (uint32_t *)(base + p.wrel);
+    a.tcnt = (uint32_t *)(base + p.tcnt);
+    a.tpre = (uint32_t *)(base + p.tpre);
+    a.dst = (int32_t *)(base + p.dst);
+    a.kept = kept_seq ? (int64_t *)(base + p.kept) : nullptr;
+    if (p.flag_grid > 0) {
+        Timer t(c, "lc_flag");
+        launch_lc_flag(a, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(a, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t live = 0;
+    HIPCHK(c, hipMemcpy(&live, a.tpre + p.nt, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)live > c->head)
+        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (log head)", live, (long long)c->head);
+    if (expect_kept >= 0 && expect_kept != (int64_t)live)
+        return fail(c, FB_ESTATE, "the log holds %u live entries, the caller expected %lld", live, (long long)expect_kept);
+    if (kept_seq && cap < (int64_t)live)
+        return fail(c, FB_EINVAL, "kept_seq holds %lld entries, the log %u live ones", (long long)cap, live);
+    if (p.move.grid() > 0) {
+        Timer t(c, "lc_move");
+        launch_lc_move(a, t.st());
+    }
+    if (live) {
+        Timer t(c, "lc_copy");
+        launch_copy_words((uint32_t *)c->log_slot, (const uint32_t *)a.dst, (int64_t)live, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    if (kept_seq && live) HIPCHK(c, hipMemcpy(kept_seq, a.kept, (size_t)live * 8, hipMemcpyDeviceToHost));
+    c->head = (int64_t)live;
+    c->stale_any = false;  // a compacted log holds only live entries
+    c->launched = c->waited = false;  // (the discarded FB_ENOSPC tick)
+    c->l_enospc = false;
+    if (n_kept) *n_kept = (int64_t)live;
     return FB_OK;
 }
 
@@ -2004,6 +2090,7 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     c->l_resort = false;
     c->launched = true;
     c->waited = false;
+    c->l_enospc = false;
     c->l_purge_only = c->next_purge_only;
     c->next_purge_only = false;
     c->l_win = win_plan(c);
@@ -2163,6 +2250,7 @@ int fb_tick_wait(fb_ctx *c, fb_tick_result *res) {
         }
         if (c->hout->status == 0) break;
         c->l_eager = false;
+        if (c->hout->status == 2) c->l_enospc = true;
         if (c->hout->status == 2)
             return fail(c, FB_ENOSPC, "in-flight log full: %lld entries + this tick's dispatches exceed %lld",
                         (long long)c->l_head, (long long)c->log_cap);

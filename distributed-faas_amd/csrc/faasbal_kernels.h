@@ -529,5 +529,23 @@ void launch_copy_multi(const CopyMulti &m, Stream st);
 // the dense orphan list from per-tile segments (dst may be host-mapped memory): the
 // segments concatenated in tile order (each is ascending already, so the list is)
 void launch_orph_gather(int64_t *dst, const int64_t *src, const uint32_t *cnt, int ntile, Stream st);
+// fb_log_compact (grids and the scratch regions: lc_plan, faasbal_layout.h).  Entry q of the
+// log is live iff log[q] >= 0 and (live_chk: entries of dead registrations may be in the
+// log) its slot holds a record and q >= epoch[slot] -- k_log_normalize's rule.
+struct LcArgs {
+    const int32_t *log;
+    int64_t head;
+    int W, nt, live_chk;
+    const uint8_t *reg;
+    uint32_t *epoch;             // read by the flag pass, remapped by the move pass
+    unsigned long long *bitmap;  // [nt * kLcWords] live bits
+    uint32_t *wrel;              // [nt * kLcWords] live entries of the tile before the word
+    uint32_t *tcnt, *tpre;       // [nt] live entries of a tile, [nt + 1] before it
+    int32_t *dst;                // [live] the survivors' slots in order
+    int64_t *kept;               // [live] their old sequences (null: not wanted)
+};
+void launch_lc_flag(const LcArgs &a, Stream st);
+void launch_lc_scan(const LcArgs &a, Stream st);
+void launch_lc_move(const LcArgs &a, Stream st);
 
 }  // namespace fb

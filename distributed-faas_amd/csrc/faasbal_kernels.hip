@@ -5022,6 +5022,125 @@ __global__ __launch_bounds__(kBS) void k_copy_words(uint32_t *__restrict__ dst, 
     }
 }
 
+// ------------------------------------------------------------ log compaction
+// fb_log_compact (layout: lc_plan, faasbal_layout.h).  A wave streams one tile: lane l reads
+// entry 64 j + l of the tile for word j, eight words' loads in flight (each a 256-byte wave
+// load), and a ballot per word is that word of the live bitmap.  The liveness gathers
+// (live_chk) are branch-free: index clamped to slot 0, masked afterwards.
+constexpr int kLcBatch = 8;
+
+__global__ __launch_bounds__(kBS) void k_lc_flag(LcArgs a) {
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.nt) return;  // (the whole wave)
+    const int lane = lane_id();
+    const int64_t q0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine = 0;  // lane j < kLcWords: word j of the tile
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch];
+        bool live[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t q = q0 + (int64_t)(j0 + k) * 64;
+            s[k] = a.log[q < a.head ? q : a.head - 1];
+        }
+        if (a.live_chk) {
+            uint8_t r[kLcBatch];
+            uint32_t e[kLcBatch];
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int32_t sc = s[k] > 0 ? s[k] : 0;
+                r[k] = a.reg[sc];
+                e[k] = a.epoch[sc];
+            }
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
+                live[k] = q < a.head && s[k] >= 0 && r[k] && (uint64_t)q >= (uint64_t)e[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) live[k] = q0 + (int64_t)(j0 + k) * 64 < a.head && s[k] >= 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const unsigned long long m = __ballot(live[k]);
+            if (lane == j0 + k) mine = m;
+        }
+    }
+    const uint32_t cnt = (uint32_t)__popcll(mine);
+    const uint32_t inc = wave_incl_scan_u32(cnt);
+    if (lane < kLcWords) {
+        a.bitmap[(int64_t)tile * kLcWords + lane] = mine;
+        a.wrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
+    }
+    if (lane == 63) a.tcnt[tile] = inc;
+}
+
+// tpre[t] = live entries before tile t; tpre[nt] = all of them (one workgroup)
+__global__ __launch_bounds__(kBS) void k_lc_scan(LcArgs a) {
+    __shared__ uint32_t l4[kWaves];
+    uint32_t carry = 0;
+    for (int b = 0; b < a.nt; b += kBS) {
+        const int i = b + (int)threadIdx.x;
+        const uint32_t v = i < a.nt ? a.tcnt[i] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan_u32(v, l4, tot);
+        if (i < a.nt) a.tpre[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) a.tpre[a.nt] = carry;
+}
+
+// Tile workgroups: survivor q of word j goes to tpre[tile] + wrel[word] + its rank in the
+// word (mbcnt of the bitmap word: no atomics); out of place, fb_log_compact copies dst back.
+// Slot workgroups: epoch[s] = live entries below min(epoch[s], head), the same rank query.
+__global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
+    const LcMoveLayout lay = lc_move_layout(a.nt, a.W);
+    const int bid = (int)blockIdx.x;
+    if (bid >= lay.end(kLcMoveTiles)) {
+        const int s = lay.rel(kLcMoveSlots, bid) * kBS + (int)threadIdx.x;
+        if (s >= a.W) return;
+        const uint64_t e = a.epoch[s];
+        uint32_t r;
+        if (e >= (uint64_t)a.head) {
+            r = a.tpre[a.nt];
+        } else {
+            const int64_t w = (int64_t)(e >> 6);
+            r = a.tpre[e / kLcTile] + a.wrel[w] + (uint32_t)__popcll(a.bitmap[w] & ((1ull << (e & 63)) - 1ull));
+        }
+        a.epoch[s] = r;
+        return;
+    }
+    const int tile = bid * kWaves + wave_id();
+    if (tile >= a.nt) return;  // (the whole wave)
+    const int lane = lane_id();
+    const int64_t q0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine = 0;
+    uint32_t pre = 0;
+    if (lane < kLcWords) {
+        mine = a.bitmap[(int64_t)tile * kLcWords + lane];
+        pre = a.tpre[tile] + a.wrel[(int64_t)tile * kLcWords + lane];
+    }
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t q = q0 + (int64_t)(j0 + k) * 64;
+            s[k] = a.log[q < a.head ? q : a.head - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const unsigned long long m = __shfl(mine, j0 + k, 64);
+            const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
+            if ((m >> lane) & 1ull) {  // (a set bit: q < head)
+                const int64_t o = (int64_t)p + popc_lt(m);
+                a.dst[o] = s[k];
+                if (a.kept) a.kept[o] = q0 + (int64_t)(j0 + k) * 64;
+            }
+        }
+    }
+}
+
 }  // namespace fb
 
 // ------------------------------------------------------------ launchers
@@ -5107,6 +5226,18 @@ void launch_log_normalize(int32_t *log, int64_t n, const uint8_t *reg, const uin
     if (n <= 0) return;
     const int grid = (int)std::min<int64_t>(cdiv(n, kBS), 8192);
     hipExtLaunchKernelGGL(k_log_normalize, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, log, n, reg, epoch);
+}
+void launch_lc_flag(const LcArgs &a, Stream st) {
+    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
+    if (p.flag_grid > 0) hipExtLaunchKernelGGL(k_lc_flag, dim3(p.flag_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_lc_scan(const LcArgs &a, Stream st) {
+    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
+    hipExtLaunchKernelGGL(k_lc_scan, dim3(p.scan_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_lc_move(const LcArgs &a, Stream st) {
+    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
+    if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lc_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_gate(uint32_t *flag, uint32_t want, uint64_t limit, Stream st) {
     hipExtLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st.s, st.e0, st.e1, 0, flag, want, limit);

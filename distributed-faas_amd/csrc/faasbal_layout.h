@@ -257,6 +257,54 @@ FB_HD CopyMultiLayout copy_multi_layout(const CopyMulti &m) {
 }
 
 // ---------------------------------------------------------------------------------------
+// fb_log_compact: three launches over the log's kLcTile-entry tiles, a wave per tile (four
+// per workgroup), and the scratch they share.
+//   k_lc_flag  a workgroup per four tiles: the live bitmap (kLcWords 64-bit words per tile,
+//              whole tiles: bits past the head are 0), each word's live count before it in
+//              its tile (wrel), each tile's live count (tcnt)
+//   k_lc_scan  one workgroup: tpre[t] = live entries before tile t, tpre[nt] = all of them
+//   k_lc_move  the tile workgroups scatter the survivors (dst, and kept: their old
+//              sequences), then a workgroup per kBS slots remaps the epochs
+// lc_plan states the grids, the counts and the scratch's regions (256-byte aligned byte
+// offsets) for a log of `head` entries and W slots; the launchers and the allocation both
+// read them from it (tests/lc_probe.cpp walks it on the CPU).
+constexpr int kLcTile = kFTile;
+constexpr int kLcWords = kLcTile / 64;
+enum { kLcMoveTiles, kLcMoveSlots };
+struct LcMoveLayout : Roles<2> {};
+FB_HD LcMoveLayout lc_move_layout(int nt, int W) { return {{{quarter(nt), (int)cdiv(W, kBS)}}}; }
+struct LcPlan {
+    int nt;      // tiles
+    int64_t nw;  // bitmap words
+    int flag_grid, scan_grid;
+    LcMoveLayout move;
+    size_t bitmap, wrel, tcnt, tpre, dst, kept;  // regions: nw x 8, nw x 4, nt x 4, (nt + 1) x 4, head x 4, head x 8 bytes
+    size_t bytes;
+};
+inline LcPlan lc_plan(int64_t head, int W, bool want_kept) {
+    LcPlan p{};
+    p.nt = (int)cdiv(head, kLcTile);
+    p.nw = (int64_t)p.nt * kLcWords;
+    p.flag_grid = quarter(p.nt);
+    p.scan_grid = 1;
+    p.move = lc_move_layout(p.nt, W);
+    size_t o = 0;
+    auto take = [&o](size_t b) {
+        const size_t at = o;
+        o += (b + 255) & ~(size_t)255;
+        return at;
+    };
+    p.bitmap = take((size_t)p.nw * 8);
+    p.wrel = take((size_t)p.nw * 4);
+    p.tcnt = take((size_t)p.nt * 4);
+    p.tpre = take(((size_t)p.nt + 1) * 4);
+    p.dst = take((size_t)head * 4);
+    p.kept = take(want_kept ? (size_t)head * 8 : 0);
+    p.bytes = o;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------
 // The died bitmap (a bit per slot, 64-bit words) staged in dynamic LDS by whole int4: the
 // bytes a launch requests and the int4 count the kernel's copy loops over.
 struct BitmapLds {

@@ -241,6 +241,24 @@ class GpuBalancer:
         self._chk(self.lib.fb_read_inflight(self.h, _p(out)))
         return out[: self.n_workers]
 
+    def compact_log(self, expect=None, want_kept=True):
+        """fb_log_compact: renumber the in-flight log densely on the device (completed
+        entries and those of dead registrations dropped, survivors in order, epochs
+        remapped); everything else of the state, the tick pipeline's included, stays.
+        ``expect``: the live count the caller's mirror holds (FB_ESTATE and nothing changes
+        when the device disagrees).  Returns dict(n_kept, kept): ``kept[new] = old``
+        sequence (int64, ascending), or None without ``want_kept``."""
+        n = C.c_int64()
+        if not want_kept:
+            self._chk(self.lib.fb_log_compact(self.h, -1 if expect is None else int(expect), None, 0, C.byref(n)))
+            return {"n_kept": n.value, "kept": None}
+        # the live count is known only when the caller states it: else room for the whole log
+        cap = int(expect) if expect is not None else self.read_state(with_log=False)["head"]
+        kept = np.zeros(max(cap, 1), np.int64)
+        self._chk(self.lib.fb_log_compact(self.h, -1 if expect is None else int(expect),
+                                          kept.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return {"n_kept": n.value, "kept": kept[: n.value]}
+
     # ----------------------------------------------------------------- ticks
     def launch(self, now, tte, ev_kind=(), ev_slot=(), ev_val=(), ev_ts=(), ev_seq=None, n_pending=0):
         if not len(ev_kind) and not len(ev_slot):

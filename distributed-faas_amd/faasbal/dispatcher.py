@@ -44,7 +44,7 @@ import time
 import numpy as np
 
 from . import codec
-from ._lib import FB_ENOSPC, FB_EVS_RECONNECT, FaasbalError
+from ._lib import FB_ENOSPC, FB_ESTATE, FB_EVS_RECONNECT, FaasbalError
 from .balancer import GpuBalancer
 
 EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER = 0, 1, 2, 3, 4
@@ -120,6 +120,7 @@ class GpuPushDispatcher:
         self.balancer.load_state(np.zeros(W, np.uint8), np.zeros(W, np.int32), np.zeros(W, np.float64))
         self.ticks = 0
         self.compactions = 0
+        self.device_compactions = 0                    # ... of which on the device (fb_log_compact)
 
     @classmethod
     def subclass_of(cls, base):
@@ -454,7 +455,29 @@ class GpuPushDispatcher:
     def compact_log(self):
         """Renumber the in-flight log densely (completed and redistributed entries
         dropped); epochs are remapped so every registration keeps exactly its own
-        in-flight entries.  Host O(F), called only when the log would overflow."""
+        in-flight entries.  Called only when the log would overflow.  A balancer with
+        ``compact_log`` (a one-GPU ``GpuBalancer``: fb_log_compact) renumbers on the
+        device and keeps its tick pipeline; the host only remaps its own two dicts from
+        the kept list.  Otherwise (shard groups, or a device log that disagrees with
+        ``inflight``) the host path: the whole state read, renumbered and loaded again."""
+        device = getattr(self.balancer, "compact_log", None)
+        if callable(device):
+            try:
+                out = device(expect=len(self.inflight))
+            except FaasbalError as e:
+                if e.code != FB_ESTATE:
+                    raise
+                out = None
+            if out is not None:
+                remap = {int(q): i for i, q in enumerate(out["kept"])}
+                if any(q not in remap for q in self.inflight):  # (same count, other entries)
+                    raise FaasbalError(FB_ESTATE, "the device log's live entries are not the in-flight table's")
+                self.inflight = {remap[q]: v for q, v in self.inflight.items()}
+                self.task_seq = {tid: remap[q] for tid, q in self.task_seq.items()}
+                self.head = int(out["n_kept"])
+                self.compactions += 1
+                self.device_compactions += 1
+                return
         st = self.balancer.read_state(with_log=True)
         keep = np.asarray(sorted(self.inflight), np.int64)
         log = np.asarray([self.inflight[q][1] for q in keep], np.int32)

@@ -79,6 +79,9 @@ class ShardedBalancer(GpuBalancer):
     def load_state(self, *a, **k):
         raise FaasbalError(_lib.FB_ESTATE, "sharded context: use load() with the global state")
 
+    # fb_log_compact refuses sharded contexts (sequence numbers are global across ranks)
+    compact_log = None
+
     def load(self, st):
         """Load this rank's part of a global state dict."""
         sh = split_state(st, self.world, self.rank)

@@ -103,6 +103,23 @@ int fb_read_state(fb_ctx *ctx, uint8_t *registered, int32_t *free_processes,
  * the count of the slot's entries that are neither completed nor redistributed). */
 int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
 
+/* One-GPU contexts (heartbeat and deque), between ticks: renumber the in-flight log densely.
+ * Entry q survives iff it is live: log_slot[q] >= 0 and, on heartbeat contexts, its slot holds a
+ * record and q >= epoch[slot] (the rule of k_log_normalize / fb_load_state).  Survivors keep their
+ * order; new sequence = number of survivors below q.  Every slot's epoch becomes the number of
+ * survivors below min(epoch, log_head).  log_head becomes *n_kept.  Nothing else of the committed
+ * state changes (records, queue / window, free counts, in-flight counts, round hints), and the
+ * tick pipeline keeps its state (a window stays a window).
+ * kept_seq (may be NULL; cap entries): old sequence of each new sequence, ascending.
+ * expect_kept >= 0: if the live count differs, FB_ESTATE and nothing changes (a host mirror that
+ * disagrees).  cap < live count with kept_seq != NULL: FB_EINVAL and nothing changes.
+ * FB_ESTATE also: a sharded context (its sequence numbers are global across ranks: compacting
+ * them needs a collective), staged events pending, a tick launched but not waited, or waited
+ * but not committed.  A tick whose fb_tick_wait failed with FB_ENOSPC is discarded (launch it
+ * again with the new sequences), as fb_load_state discards it.
+ * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
+int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept);
+
 /* Enqueue one tick on the context's stream (no host sync).
  * Replaces, per tick: the inbound branches (task_dispatcher.py:343-387), the
  * purge (:241-249, called at :390) and the dispatch block (:393-419), plus the
