@@ -304,6 +304,13 @@ struct fb_ctx {
     bool xz_ok = false;
     int phase = 0;                                    // 1: phase 1 enqueued; 2: phase 2 enqueued
     int shard_R = 0;                                  // > 0: round rows a relaunch asked for (FB_ERERUN)
+    // sharded: results clear their log entries in place at launch; the entries a launch
+    // cleared (per message, tagged with the launch's stamp) are named again by the next
+    // launch unless the tick was committed in between
+    int64_t *undo_idx = nullptr;
+    unsigned long long *undo_key = nullptr;
+    uint32_t undo_tag = 0;
+    int undo_E = 0;                                   // > 0: messages of a launch not committed yet
     hipStream_t own_s = nullptr;                      // the context's own stream (fb_set_stream may borrow another)
 };
 
@@ -746,6 +753,9 @@ EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const
     ea.lstamp = defer ? c->lstamp : 0;
     ea.bud = c->bud;
     ea.post_infl = c->post_infl;
+    ea.undo_idx = c->undo_idx;
+    ea.undo_key = c->undo_key;
+    ea.undo_tag = c->lstamp;
     if (p.grouping == Grouping::sort) {
         ea.deque = c->deque;
         ea.tokcnt_in = c->tokcnt[cur];
@@ -1343,6 +1353,8 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
         ap.add(&c->xg_tk, ng);
         ap.add(&c->xs_tk, (size_t)64);  // k_xscan's ticket (zero: the arena is zeroed, the last workgroup resets it)
         ap.add(&c->ogrp, ng * kXGroupR);
+        ap.add(&c->undo_idx, E);
+        ap.add(&c->undo_key, E);
     }
     int rc = arena_commit(c, ap);
     if (!rc && hipMemset(c->bad_min, 0x7f, 4) != hipSuccess) rc = fail(c, FB_EHIP, "hipMemset(bad_min) failed");
@@ -1693,6 +1705,7 @@ int fb_load_shard(fb_ctx *c, int32_t slot_base, int32_t n_workers, const uint8_t
     c->maxc_hint = 1;
     c->launched = c->waited = false;
     c->phase = 0;
+    c->undo_E = 0;  // an abandoned launch's notes name entries of the log this one replaced
     return FB_OK;
 }
 
@@ -2101,7 +2114,22 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     c->hout->new_qlen = -1;
     c->hout->win_head = -1;
     c->hout->win_qlen = -1;
+    if (c->undo_E > 0) {
+        // the last launch was never committed (abandoned, failed, or asked for this relaunch):
+        // the log entries its results completed are in flight again
+        {
+            Timer t(c, "log_undo");
+            launch_log_undo(c->log_slot, c->undo_idx, c->undo_key, c->undo_tag, c->undo_E, t.st());
+        }
+        HIPCHK(c, hipGetLastError());
+        c->undo_E = 0;
+    }
+    const uint32_t stamp0 = c->lstamp;
     const int rc = enqueue_tick(c);
+    if (c->undo_idx && c->lstamp != stamp0) {  // (phase 1 was enqueued under a stamp of its own)
+        c->undo_E = E;
+        c->undo_tag = c->lstamp;
+    }
     if (rc) return rc;
     c->l_eager = false;
     if (c->eager && c->l_win) {
@@ -2393,6 +2421,7 @@ int fb_tick_commit(fb_ctx *c) {
     // sharded: a tick that needed a wide table keeps it for the next one while the fill
     // level stays beyond the narrow table (no relaunch per tick)
     if (c->shard) c->shard_R = c->last.fill_level + 2 > kRFused ? c->l_R : 0;
+    c->undo_E = 0;  // the tick's completed entries stay completed
     c->head = c->last.log_head;
     c->head_local += c->shard ? c->last.n_local : 0;
     c->Qtrue = c->last.queue_len;

@@ -219,6 +219,12 @@ struct EvArgs {
     int slot_base, W;
     int64_t head_local; // sharded: local log length (entries carry their global seq in lseq)
     const uint32_t *lseq;
+    // sharded: a result clears its log entry in place; message i notes the entry it cleared
+    // and {this launch's tag, slot}, so the next launch can take back an abandoned launch's
+    // clears (k_log_undo).  Null elsewhere
+    int64_t *undo_idx;
+    unsigned long long *undo_key;
+    uint32_t undo_tag;
     uint32_t tick;
     double tte;
     int64_t head_in;
@@ -504,6 +510,9 @@ void launch_emit_win(const TickArgs &a, Stream st);
 // k_emit_win workgroups resident per CU at once (the occupancy calculator; 0 on failure)
 int emit_win_resident_per_cu();
 void launch_pos_rebuild(int32_t *pos, const int32_t *queue, const int32_t *qfree, int64_t off, int64_t n, Stream st);
+// sharded: the log entries that the abandoned launch `tag` cleared in place, named again
+void launch_log_undo(int32_t *log_slot, const int64_t *undo_idx, const unsigned long long *undo_key, uint32_t tag,
+                     int n, Stream st);
 // evicted slots in ascending order from the per-slot status bytes and per-tile counts (two
 // launches: a one-workgroup scan of the tile counts, then one block per tile)
 void launch_evict_gather(int32_t *dst, const uint8_t *st, const uint32_t *wcnt, int64_t *wpre, int W, Stream s);

@@ -716,7 +716,15 @@ struct SlotRun {
                     if (a.log_slot[q] == (int32_t)gs) cleared = atomicExch(&a.ctag[q], a.lstamp) != a.lstamp;
                 } else {
                     const int64_t li = a.shard ? lseq_find(a.lseq, a.head_local, q) : q;
-                    if (li >= 0 && a.log_slot[li] == (int32_t)gs) a.log_slot[li] = -1;
+                    if (li >= 0 && a.log_slot[li] == (int32_t)gs) {
+                        a.log_slot[li] = -1;
+                        // sharded: cleared in place (this tick's log scan reads it), and noted
+                        // for k_log_undo should the launch be abandoned
+                        if (a.undo_idx) {
+                            a.undo_idx[i] = li;
+                            a.undo_key[i] = ((unsigned long long)a.undo_tag << 32) | gs;
+                        }
+                    }
                 }
             }
             if (fr == 1 && !inq) { inq = 1; qstat = kQsBack; qidx = i; }
@@ -5338,6 +5346,23 @@ void launch_evict_gather(int32_t *dst, const uint8_t *st, const uint32_t *wcnt, 
     hipExtLaunchKernelGGL(k_wscan, dim3(1), dim3(kBS), 0, s.s, s.e0, nullptr, 0, wcnt, nt, wpre);
     hipExtLaunchKernelGGL(k_evict_compact, dim3(nt), dim3(kBS), 0, s.s, nullptr, s.e1, 0, dst, st, (const int64_t *)wpre, W);
 }
+// An abandoned sharded launch's in-place clears, taken back: message i of that launch (its
+// tag in undo_key[i]'s high word) completed local entry undo_idx[i] of the slot in the low word.
+__global__ __launch_bounds__(kBS) void k_log_undo(int32_t *log_slot, const int64_t *undo_idx,
+                                                  const unsigned long long *undo_key, uint32_t tag, int n) {
+    const int i = blockIdx.x * kBS + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = undo_key[i];
+    if ((uint32_t)(key >> 32) == tag) log_slot[undo_idx[i]] = (int32_t)(uint32_t)key;
+}
+
+void launch_log_undo(int32_t *log_slot, const int64_t *undo_idx, const unsigned long long *undo_key, uint32_t tag,
+                     int n, Stream st) {
+    if (n > 0)
+        hipExtLaunchKernelGGL(k_log_undo, dim3(cdiv(n, kBS)), dim3(kBS), 0, st.s, st.e0, st.e1, 0, log_slot, undo_idx,
+                              undo_key, tag, n);
+}
+
 void launch_pos_rebuild(int32_t *pos, const int32_t *queue, const int32_t *qfree, int64_t off, int64_t n, Stream st) {
     if (n > 0)
         hipExtLaunchKernelGGL(k_pos_rebuild, dim3(cdiv(n, kBS)), dim3(kBS), 0, st.s, st.e0, st.e1, 0, pos, queue, qfree,

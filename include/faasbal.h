@@ -128,7 +128,9 @@ int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t 
  * n_pending = tasks waiting in pub/sub (carried-over ones first).
  * Reads the committed state, writes the tick's outputs and the next state into
  * separate buffers: launching again without fb_tick_commit recomputes the same
- * tick (used by the benchmark). */
+ * tick (used by the benchmark).  Sharded contexts clear the log entries that results
+ * complete in place; a launch after a tick that was never committed first restores
+ * them, so it may carry other messages. */
 int fb_tick_launch(fb_ctx *ctx, double now, double tte, int32_t n_events, const uint8_t *kind,
                    const int32_t *slot, const int32_t *val, const double *ts, const int64_t *seq,
                    int64_t n_pending);

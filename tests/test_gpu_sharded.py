@@ -29,7 +29,10 @@ def _group(st, world, log_cap, max_events=4096, purge_mode=1):
     return bals, o
 
 
-def _group_tick(bals, *args, relaunches=None):
+def _group_tick(bals, *args, relaunches=None, on_attempt=None, commit=True):
+    """One tick of the group.  ``on_attempt(attempt)`` runs after every launch was waited
+    for (a relaunch asked by FB_ERERUN included); ``commit=False`` leaves the tick waited
+    but uncommitted on every rank."""
     import torch
     from faasbal import FaasbalError
     from faasbal._lib import FB_ERERUN
@@ -53,6 +56,8 @@ def _group_tick(bals, *args, relaunches=None):
                 res.append(b.wait())
             except FaasbalError as e:
                 codes.add(e.code)
+        if on_attempt is not None:
+            on_attempt(attempt)
         if not codes:
             break
         assert codes == {FB_ERERUN}, codes  # a relaunch is asked of every rank or of none
@@ -69,14 +74,23 @@ def _group_tick(bals, *args, relaunches=None):
     for b in bals[1:]:
         np.testing.assert_array_equal(outs[0]["reconnect"], b.event_status())
     merged = merge_outputs(outs, res[0]["n_assigned"])
-    for b in bals:
-        b.commit()
+    if commit:
+        for b in bals:
+            b.commit()
     return merged, res[0]
 
 
-def _cmp(bals, o, a, b, t):
+def _cmp_outputs(a, b, t):
     for k in ("reconnect", "assign", "orphans", "evicted"):
         np.testing.assert_array_equal(a[k], b[k], err_msg="tick %d: %s" % (t, k))
+
+
+def _cmp(bals, o, a, b, t):
+    _cmp_outputs(a, b, t)
+    _cmp_state(bals, o, t)
+
+
+def _cmp_state(bals, o, t):
     so = o.export()
     reg = so["reg"].astype(bool)
     glog = np.full(len(so["log"]), -1, np.int32)

@@ -357,3 +357,21 @@ def test_window_and_lds_limits(probe):
                     assert int(ks["k_logscan"]["lds"]) == _logscan_bytes(W) <= max_lds
                 if a["f_emit"] == "1":
                     assert int(ks["k_emit2"]["lds"]) == _logscan_bytes(W) - 16 <= max_lds
+
+
+def test_xcfirst_defaults_on_at_the_knob_shapes(probe):
+    """tests/test_gpu_shard_forms.py runs its ladder and its 65 792-position scenario at world 2
+    with xcfirst = 0: that is another launch order only where xcfirst defaults to 1
+    (4 x (log + slot workgroups) > queue workgroups).  Every xplan phase 2 of both scenarios,
+    on both ranks, asked of plan_tick."""
+    import test_gpu_shard_forms as sf
+
+    n = 0
+    for scen, forms in ((sf._edge(65_792, 32), sf._edge_forms(32)), (sf._ladder(), sf.LADDER_FORMS)):
+        fields = [(t, r, f) for t, r, f in sf.plan_fields(scen, 2) if forms[t][0] == "xplan"]
+        for (t, r, f), a in zip(fields, probe([("plan", f) for _, _, f in fields])):
+            assert _stages(a) == ["plan", "emit"] and a["xplan"] == "1", (t, r, a)
+            assert a["xcfirst"] == "1", (t, r, f)
+            n += 1
+    assert n == 2 * (3 + sum(m[0] == "xplan" for m in sf.LADDER_FORMS))
+
