@@ -51,6 +51,36 @@ constexpr int kRsItems = FAASBAL_RS_ITEMS;  // radix sort: keys per thread per t
 constexpr int kRsTile = kBS * kRsItems;
 constexpr int kRFused = 128;       // fused tick: round table of at most 128 rows ...
 constexpr int kTabLd = 16;         // ... read by at most 16 int4 loads per thread
+// Group rows (fused and sharded ticks): 2^gshift queue blocks add into one row, the smallest
+// gshift with 4^gshift >= nbq and at most 64 rows, so a k_emit2 queue block reads about
+// 2 sqrt(nbq) rows: every group row plus the rows of the earlier blocks of its own group.
+__host__ __device__ constexpr int group_shift(int64_t nbq) {
+    int gs = 0;
+    while (((int64_t)1 << (2 * gs)) < nbq || cdiv(nbq, (int64_t)1 << gs) > 64) ++gs;
+    return gs;
+}
+// ... and the most loads per thread that takes on a fused tick (nbq * R <= kTabLd * kBS * 4;
+// thread t holds part t mod (kBS / R) of round column t / (kBS / R)), over every such nbq:
+// of the group rows (blk = false) or of the earlier block rows (blk = true).  k_emit2's
+// fused queue role issues that many clamped loads in one round, whatever the queue.
+constexpr int fused_row_loads(int R, bool blk) {
+    int m = 0;
+    for (int nbq = 1; nbq * R <= kTabLd * kBS * 4; ++nbq) {
+        const int gsz = 1 << group_shift(nbq), ng = (int)cdiv(nbq, gsz);
+        const int rows = blk ? (nbq < gsz ? nbq : gsz) - 1 : ng;
+        const int ld = (int)cdiv(rows, kBS / R);
+        m = ld > m ? ld : m;
+    }
+    return m;
+}
+constexpr int kGrpLd = 4;          // group / block row loads per thread per batch (k_plan2, k_emit2)
+constexpr int kBlkLdWide = 8;      // fused, R > 32: block row loads per thread
+static_assert(fused_row_loads(32, false) <= kGrpLd && fused_row_loads(64, false) <= kGrpLd &&
+                  fused_row_loads(128, false) <= kGrpLd,
+              "fused k_emit2: the group rows in kGrpLd loads per thread");
+static_assert(fused_row_loads(32, true) <= kGrpLd && fused_row_loads(64, true) <= kBlkLdWide &&
+                  fused_row_loads(128, true) <= kBlkLdWide,
+              "fused k_emit2: a group's earlier block rows in kGrpLd (R = 32) / kBlkLdWide loads per thread");
 constexpr int kPeel = 4;           // fused tick: block-count arrays of at most 4*256 entries
 constexpr int kLdsBitmapSlots = 1 << 17;  // died bitmap staged in LDS up to 128K slots (16 KB)
 constexpr int kLsBS = 1024;        // k_logscan: one 16-wave workgroup per CU

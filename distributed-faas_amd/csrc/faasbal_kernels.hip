@@ -1281,13 +1281,19 @@ __device__ __forceinline__ bool is_dead(const TickArgs &a, const Cur &c) { retur
 // One load from the list the position falls in (no branch per list).  The list
 // pointers go through registers first: a select between the fields' addresses
 // would keep the kernels' argument copy in scratch.
+// (... and lose their address space there: the load is made a global one again by hand.  A
+// flat load counts against the scalar counter too, so the next wait for an argument field
+// would wait for it -- a memory round in the middle of a prologue.)
+// IDLE_Q: a tick without messages has no lists, so every position is the queue's (for a
+// caller that would otherwise branch on E == 0 around its loads).
+template <bool IDLE_Q = false>
 __device__ __forceinline__ int lq_slot(const TickArgs &a, int64_t pos) {
-    const bool fr = pos < a.E, qu = !fr && pos < a.E + a.Qn;
+    const bool fr = pos < a.E, qu = !fr && (pos < a.E + a.Qn || (IDLE_Q && a.E == 0));
     const int32_t *pf = a.front_list, *pq = a.queue_in, *pb = a.back_list;
     asm("" : "+s"(pf), "+s"(pq), "+s"(pb));
     const int32_t *p = fr ? pf : (qu ? pq : pb);
     const int64_t i = fr ? pos : (qu ? pos - a.E : pos - a.E - a.Qn);
-    return p[i] - (qu ? 0 : 1);
+    return *(const __attribute__((address_space(1))) int32_t *)(p + i) - (qu ? 0 : 1);
 }
 // Local index of global slot s if this rank owns it, else -1 (one GPU: s itself).
 __device__ __forceinline__ int own_slot(const TickArgs &a, int s) {
@@ -2518,7 +2524,6 @@ __global__ __launch_bounds__(kBS) void k_xscan(TickArgs a) {
 // (a streaming tick: 2 of 64 columns) -- instead of k_plan's one workgroup per
 // round walking a column of every block.  Two more workgroups scan the orphan /
 // eviction tile counts.  Group 0 publishes the totals (A, P).
-constexpr int kGrpLd = 4;     // group / block row loads per thread per batch (k_plan2, k_emit2)
 constexpr int kP2Rows = kBS;  // rows per pass of a group's scan (one per thread)
 // k_plan2's group scan for groups of <= 64 blocks (one wave; lane l = block b0 + l)
 template <int R>
@@ -3348,20 +3353,17 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
         const int R = a.R;       // 32, 64 or 128
         // ---- every load in flight at once (clamped indices, no branches)
         const int64_t pq = pos < a.Qlog ? pos : (a.Qlog > 0 ? a.Qlog - 1 : 0);
-        int32_t raw0;
-        double hb0;
-        if (a.cq_direct) {
-            // idle tick: the committed position's free count and heartbeat, k_scan's liveness
-            // test repeated (the same bytes k_scan would have copied into c_arr / c_hb)
-            const double hq = a.qhb_in[pq];
-            const int32_t fq = a.qfree_in[pq];
-            hb0 = hq;
-            raw0 = ((a.now - hq) > a.tte) ? INT32_MIN : fq;
-        } else {
-            raw0 = a.c_arr[pq];
-            hb0 = a.c_hb[pq];
-        }
-        const int s0 = a.E == 0 ? a.queue_in[pq] : lq_slot(a, pq);
+        // idle tick (cq_direct): the committed position's free count and heartbeat, k_scan's
+        // liveness test repeated (the same bytes k_scan would have copied into c_arr / c_hb).
+        // One pair of loads through the form's own pointers, the test applied as a mask: a
+        // branch per source would finish its loads -- a memory round -- before the loads
+        // below are issued
+        const double *hbp = a.cq_direct ? a.qhb_in : a.c_hb;
+        const int32_t *cp = a.cq_direct ? a.qfree_in : a.c_arr;
+        const double hb0 = hbp[pq];
+        const int32_t cq0 = cp[pq];
+        const int s0 = lq_slot<true>(a, pq);  // (E == 0: queue_in[pq])
+        const int32_t raw0 = (a.cq_direct && (a.now - hb0) > a.tte) ? INT32_MIN : cq0;
         // counts of c > r in the earlier segments of this block: lane i, round 64 k + i
         // (all three earlier segments loaded unconditionally, clamped, then masked:
         // a loop bounded by the wave id would issue one load and wait per segment)
@@ -3447,7 +3449,31 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
             // whole rows; the 8 row classes of a column are summed by a cross-half shuffle and
             // the 4 waves' partials after the block barrier
             const bool trp = PM == 2 && NCH == 1 && gsz <= 64;
-            if (trp) {
+            // max c, orphans and evictions: columns R, R + 1, R + 2 of the group rows
+            // (ngrp <= 64: wave 0 holds them), in the round of the rows
+            const int gi = min((int)threadIdx.x, ng - 1) * gs + R;
+            const uint32_t mg = a.grp[gi], og = a.grp[gi + 1], eg = a.grp[gi + 2];
+            if constexpr (PM == 0) {
+                // fused: the limits bound both trip counts (fused_row_loads), so the group rows
+                // g' = p + P j and the rows of the blocks of group g before b are a fixed number
+                // of clamped loads, every one issued before the first use (a loop over the
+                // run-time counts waits for each batch before it issues the next)
+                constexpr int NB = NCH == 1 ? kGrpLd : kBlkLdWide;
+                uint32_t vg[kGrpLd], vb[NB];
+                const int nbl = nb_in > 0 ? nb_in - 1 : 0;
+#pragma unroll
+                for (int j = 0; j < kGrpLd; ++j) vg[j] = a.grp[min(p + P * j, ng - 1) * gs + r];
+#pragma unroll
+                for (int j = 0; j < NB; ++j) vb[j] = a.qcnt[(size_t)(g * gsz + min(p + P * j, nbl)) * R + r];
+#pragma unroll
+                for (int j = 0; j < kGrpLd; ++j) {
+                    const int gg = p + P * j;
+                    tot += gg < ng ? vg[j] : 0u;
+                    pre += gg < g ? vg[j] : 0u;
+                }
+#pragma unroll
+                for (int j = 0; j < NB; ++j) pre += p + P * j < nb_in ? vb[j] : 0u;
+            } else if (trp) {
                 const int cc = (int)threadIdx.x & 31, q = (int)threadIdx.x >> 5;
                 uint32_t vg[8], vb[8];
 #pragma unroll
@@ -3489,10 +3515,6 @@ __global__ __launch_bounds__(kBS) void k_emit2(TickArgs a_) {
                 for (int j = 0; j < kGrpLd; ++j) pre += p + P * (j0 + j) < nb_in ? v[j] : 0u;
             }
             }
-            // max c, orphans and evictions: columns R, R + 1, R + 2 of the group rows
-            // (ngrp <= 64: wave 0 holds them)
-            const int gi = min((int)threadIdx.x, ng - 1) * gs + R;
-            const uint32_t mg = a.grp[gi], og = a.grp[gi + 1], eg = a.grp[gi + 2];
             if (trp) {
                 if (lane < 32) {
                     gpre[w * 32 + lane] = pre;

@@ -287,7 +287,7 @@ inline void plan_tick(const PlanIn &in, TickArgs &a, TickPlan &p) {
         // workgroup each)
         int gs = 0;
         if (a.fused || p.sgrp)
-            while ((1 << (2 * gs)) < nbq || cdiv(nbq, (int64_t)1 << gs) > 64) ++gs;
+            gs = group_shift(nbq);
         else
             while (cdiv(nbq, (int64_t)1 << gs) > 64) ++gs;
         a.grp_on = 1;
