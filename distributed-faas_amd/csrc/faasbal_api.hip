@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -290,6 +291,9 @@ struct fb_ctx {
     bool l_enospc = false;                            // the launched tick's wait failed with FB_ENOSPC (log full)
     void *lc_mem = nullptr;                           // fb_log_compact's scratch (lc_plan's regions; made on first use)
     size_t lc_cap = 0;
+    void *ps_mem = nullptr;                           // fb_pool_stats' scratch (ps_plan's regions; made on first use)
+    size_t ps_cap = 0;
+    int64_t *ps_out = nullptr, *ps_out_dev = nullptr; // ... and its folded record, host-mapped (kPsCols words)
     int full_assign = 0;                              // fb_set_full_assign: phase 2 writes the whole task -> slot array
     bool l_full = false;                              // ... and the last launch did
     int32_t *assign_all = nullptr;                    // (its own allocation, grown as ticks need)
@@ -1444,6 +1448,8 @@ int fb_destroy(fb_ctx *c) {
     if (c->assign_all) hipFree(c->assign_all);
     if (c->win_owned) hipFree(c->win_mem);
     if (c->lc_mem) hipFree(c->lc_mem);
+    if (c->ps_mem) hipFree(c->ps_mem);
+    if (c->ps_out) hipHostFree(c->ps_out);
     if (c->dbg) hipFree(c->dbg);
     if (c->arena) hipFree(c->arena);
     if (c->hout) hipHostFree(c->hout);
@@ -1807,6 +1813,141 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     c->launched = c->waited = false;  // (the discarded FB_ENOSPC tick)
     c->l_enospc = false;
     if (n_kept) *n_kept = (int64_t)live;
+    return FB_OK;
+}
+
+// The committed pool summarised on the device.  The three launches write only
+// the scratch and the host-mapped record; nothing here settles the log or normalises a window,
+// so the ticks after it make the launches they would have made without it.
+int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, int32_t n_edges, fb_pool_summary *out) {
+    if (!c) return FB_EINVAL;
+    if (!out) return fail(c, FB_EINVAL, "fb_pool_stats: out is null");
+    if (n_edges < 0 || n_edges > FB_PS_MAX_EDGES)
+        return fail(c, FB_EINVAL, "n_edges %d outside [0, %d]", n_edges, FB_PS_MAX_EDGES);
+    const bool hbc = !c->deque;  // liveness exists
+    if (hbc) {
+        if (n_edges > 0 && !age_edges) return fail(c, FB_EINVAL, "age_edges is null with n_edges %d", n_edges);
+        for (int i = 0; i < n_edges; ++i)
+            if (!std::isfinite(age_edges[i]) || (i && !(age_edges[i] > age_edges[i - 1])))
+                return fail(c, FB_EINVAL, "age_edges[%d] = %g: the edges must be finite and strictly ascending", i,
+                            age_edges[i]);
+        if (!std::isfinite(now) || !std::isfinite(tte))
+            return fail(c, FB_EINVAL, "now %g / tte %g must be finite", now, tte);
+    }
+    if (c->shard)
+        return fail(c, FB_ESTATE, "fb_pool_stats on a sharded context: the pool is the group's, a summary needs a collective");
+    if (c->staged) return fail(c, FB_ESTATE, "fb_pool_stats with staged events pending: launch and commit their tick first");
+    if (c->launched && c->waited)
+        return fail(c, FB_ESTATE, "fb_pool_stats between a tick's wait and its commit: fb_tick_commit first");
+    if (c->launched)
+        return fail(c, FB_ESTATE, "fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first");
+    if (int rc_ = flush_commit(c)) return rc_;  // (observably an immediate commit)
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->ps_out) {
+        if (hipHostMalloc((void **)&c->ps_out, kPsCols * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
+            hipSuccess) {
+            c->ps_out = nullptr;
+            return fail(c, FB_ENOMEM, "hipHostMalloc(pool summary record) failed");
+        }
+        HIPCHK(c, hipHostGetDevicePointer((void **)&c->ps_out_dev, c->ps_out, 0));
+    }
+    const PsPlan p = ps_plan(c->W, c->Qn, c->head);
+    if (p.bytes > c->ps_cap) {
+        // sized for this state, doubling, never beyond a full table, queue and log
+        const size_t full = ps_plan(c->W_cap, std::max<int64_t>(c->qcap, c->Wq_cap), c->log_cap).bytes;
+        const size_t want = std::max(p.bytes, std::min(2 * c->ps_cap, full));
+        HIPCHK(c, stream_wait(c));
+        void *m = nullptr;
+        const hipError_t e = hipMalloc(&m, want);
+        if (e != hipSuccess)
+            return fail(c, FB_ENOMEM, "hipMalloc(pool summary scratch %zu B) failed: %s", want, hipGetErrorString(e));
+        if (c->ps_mem) hipFree(c->ps_mem);
+        c->ps_mem = m;
+        c->ps_cap = want;
+    }
+    char *const base = (char *)c->ps_mem;
+    PsArgs a{};
+    a.now = hbc ? now : 0.0;
+    a.tte = hbc ? tte : 0.0;
+    a.n_edges = hbc ? n_edges : 0;
+    for (int i = 0; i < a.n_edges; ++i) a.edge[i] = age_edges[i];
+    a.W = c->W;
+    a.nt = p.nt;
+    a.hb_chk = hbc ? 1 : 0;
+    a.tomb_chk = c->win_cap ? 1 : 0;
+    a.live_chk = c->stale_any ? 1 : 0;
+    a.Qn = c->Qn;
+    a.qoff = c->qoff;
+    a.head = c->head;
+    a.reg = c->reg;
+    a.free_ = c->free_[c->cur];
+    a.hb = c->hb;
+    a.bud = c->bud;
+    a.epoch = c->epoch;
+    a.queue = c->queue[c->qcur];
+    a.qfree = c->qfree[c->qcur];
+    a.log = c->log_slot;
+    a.xbits = (unsigned long long *)(base + p.xbits);
+    a.srow = (int64_t *)(base + p.srow);
+    a.qrow = (int64_t *)(base + p.qrow);
+    a.lrow = (int64_t *)(base + p.lrow);
+    a.out = c->ps_out_dev;
+    if (p.slots.grid() > 0) {
+        Timer t(c, "ps_slots");
+        launch_ps_slots(a, t.st());
+    }
+    if (p.log_grid > 0) {
+        Timer t(c, "ps_log");
+        launch_ps_log(a, t.st());
+    }
+    {
+        Timer t(c, "ps_fold");
+        launch_ps_fold(a, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    const int64_t *r = c->ps_out;
+    const int64_t W = c->W, n_reg = r[kPsReg], n_exp = r[kPsExp];
+    // device-reported numbers are checked before they are handed out
+    if (n_reg < 0 || n_reg > W)
+        return fail(c, FB_EHIP, "device-reported registered slots %lld outside [0, %lld] (slots)", (long long)n_reg, (long long)W);
+    if (n_exp < 0 || n_exp > n_reg)
+        return fail(c, FB_EHIP, "device-reported expired slots %lld outside [0, %lld] (registered)", (long long)n_exp,
+                    (long long)n_reg);
+    if (r[kPsQ] < 0 || r[kPsQExp] < 0 || r[kPsQ] + r[kPsQExp] != c->Qtrue)
+        return fail(c, FB_EHIP, "device-reported queue positions %lld + %lld differ from the queue's %lld", (long long)r[kPsQ],
+                    (long long)r[kPsQExp], (long long)c->Qtrue);
+    if (r[kPsLive] < 0 || r[kPsLiveExp] < 0 || r[kPsLive] + r[kPsLiveExp] > c->head)
+        return fail(c, FB_EHIP, "device-reported live entries %lld + %lld outside [0, %lld] (log head)", (long long)r[kPsLive],
+                    (long long)r[kPsLiveExp], (long long)c->head);
+    int64_t fsum = 0, asum = 0;
+    for (int i = 0; i < FB_PS_FREE_BINS; ++i) fsum += r[kPsFreeHist + i];
+    for (int i = 0; i <= FB_PS_MAX_EDGES; ++i) asum += r[kPsAgeHist + i];
+    if (fsum != n_reg - n_exp)
+        return fail(c, FB_EHIP, "device-reported free histogram holds %lld slots, not %lld (registered, not expired)",
+                    (long long)fsum, (long long)(n_reg - n_exp));
+    if (asum != (hbc ? n_reg : 0))
+        return fail(c, FB_EHIP, "device-reported age histogram holds %lld slots, not %lld (registered)", (long long)asum,
+                    (long long)(hbc ? n_reg : 0));
+    fb_pool_summary s{};
+    s.n_slots = W;
+    s.n_registered = n_reg;
+    s.n_expired = n_exp;
+    s.n_queued = r[kPsQ];
+    s.n_queued_expired = r[kPsQExp];
+    s.dispatchable = hbc ? r[kPsDisp] : -1;
+    s.free_total = r[kPsFree];
+    s.log_head = c->head;
+    s.inflight = r[kPsLive];
+    s.inflight_expired = r[kPsLiveExp];
+    s.inflight_max = c->bud ? r[kPsInflMax] : -1;
+    const bool any_hb = hbc && r[kPsHbN] > 0;
+    memcpy(&s.oldest_hb, &r[kPsHbMin], 8);
+    memcpy(&s.newest_hb, &r[kPsHbMax], 8);
+    if (!any_hb) s.oldest_hb = s.newest_hb = __builtin_nan("");
+    for (int i = 0; i < FB_PS_FREE_BINS; ++i) s.free_hist[i] = r[kPsFreeHist + i];
+    for (int i = 0; i <= FB_PS_MAX_EDGES; ++i) s.age_hist[i] = r[kPsAgeHist + i];
+    *out = s;
     return FB_OK;
 }
 

@@ -586,5 +586,30 @@ struct LcArgs {
 void launch_lc_flag(const LcArgs &a, Stream st);
 void launch_lc_scan(const LcArgs &a, Stream st);
 void launch_lc_move(const LcArgs &a, Stream st);
+// fb_pool_stats (grids, the partial rows' columns and the scratch regions: ps_plan,
+// faasbal_layout.h).  A slot is expired iff it holds a record and (now - hb) > tte (hb_chk:
+// heartbeat contexts; the tick's test); a log entry is live by LcArgs' rule.
+constexpr int kPsMaxEdges = 15;  // = FB_PS_MAX_EDGES
+struct PsArgs {
+    double now, tte;
+    double edge[kPsMaxEdges];    // ascending age edges (n_edges of them)
+    int n_edges;
+    int W, nt;                   // slots, log tiles
+    int hb_chk, tomb_chk, live_chk;
+    int64_t Qn, qoff, head;      // the committed queue is [qoff, qoff + Qn) of queue / qfree
+    const uint8_t *reg;
+    const int2 *free_;
+    const double *hb;
+    const int32_t *bud;          // in flight + free per slot (null: the context keeps none)
+    const uint32_t *epoch;
+    const int32_t *queue, *qfree;  // (qfree: read with tomb_chk only)
+    const int32_t *log;
+    unsigned long long *xbits;   // [cdiv(W, 64)] the expired bitmap: k_ps_slots writes, k_ps_log reads
+    int64_t *srow, *qrow, *lrow;  // a partial row per workgroup of the slot, queue and log roles
+    int64_t *out;                // [kPsCols] the folded record (host-mapped memory)
+};
+void launch_ps_slots(const PsArgs &a, Stream st);
+void launch_ps_log(const PsArgs &a, Stream st);
+void launch_ps_fold(const PsArgs &a, Stream st);
 
 }  // namespace fb

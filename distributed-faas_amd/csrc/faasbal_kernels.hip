@@ -5171,6 +5171,305 @@ __global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
     }
 }
 
+// ------------------------------------------------------------ pool summary
+// fb_pool_stats (layout: ps_plan, faasbal_layout.h): reductions and two small histograms over
+// the committed arrays, read only.  Every load is unconditional at a clamped index and masked
+// afterwards; every workgroup writes its whole partial row (no global atomics).
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// a column's neutral element and its fold (kPs* columns: sums, but for one unsigned maximum
+// and a floating minimum and maximum, none of which depends on the order)
+__device__ __forceinline__ unsigned long long ps_col_init(int c) {
+    return c == kPsHbMin ? (unsigned long long)__double_as_longlong(__builtin_huge_val())
+         : c == kPsHbMax ? (unsigned long long)__double_as_longlong(-__builtin_huge_val()) : 0ull;
+}
+__device__ __forceinline__ unsigned long long ps_col_fold(int c, unsigned long long acc, unsigned long long v) {
+    const double da = __longlong_as_double((long long)acc), dv = __longlong_as_double((long long)v);
+    return c == kPsInflMax ? (acc > v ? acc : v)
+         : c == kPsHbMin ? (unsigned long long)__double_as_longlong(fmin(da, dv))
+         : c == kPsHbMax ? (unsigned long long)__double_as_longlong(fmax(da, dv)) : acc + v;
+}
+
+__global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
+    prefetch_args(a);
+    __shared__ uint32_t hist[kWaves][64];                     // per wave: free bins, then age bins
+    __shared__ unsigned long long wv[kWaves][kPsFreeHist];    // per wave: the scalar columns
+    const PsSlotsLayout lay = ps_slots_layout(a.W, a.Qn);
+    const int bid = (int)blockIdx.x, lane = lane_id(), wave = wave_id();
+    const int wlast = a.W > 0 ? a.W - 1 : 0;
+    if (bid >= lay.end(kPsSlotsSlots)) {
+        // queue role: each position's record gathered by its slot
+        const int qb = lay.rel(kPsSlotsQueue, bid);
+        const int64_t p0 = (int64_t)qb * kPsSpan + threadIdx.x;
+        int32_t s[kPsTiles], qf[kPsTiles], f[kPsTiles];
+        double h[kPsTiles];
+#pragma unroll
+        for (int k = 0; k < kPsTiles; ++k) {
+            const int64_t p = p0 + (int64_t)k * kBS;
+            s[k] = a.queue[a.qoff + (p < a.Qn ? p : a.Qn - 1)];
+        }
+        if (a.tomb_chk) {
+#pragma unroll
+            for (int k = 0; k < kPsTiles; ++k) {
+                const int64_t p = p0 + (int64_t)k * kBS;
+                qf[k] = a.qfree[a.qoff + (p < a.Qn ? p : a.Qn - 1)];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kPsTiles; ++k) qf[k] = 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kPsTiles; ++k) {
+            const int sc = s[k] < 0 ? 0 : (s[k] > wlast ? wlast : s[k]);
+            f[k] = a.free_[sc].x;
+            h[k] = a.hb[sc];
+        }
+        uint32_t nq = 0, nqe = 0;
+        unsigned long long disp = 0;
+#pragma unroll
+        for (int k = 0; k < kPsTiles; ++k) {
+            const bool valid = p0 + (int64_t)k * kBS < a.Qn && qf[k] != kTomb;
+            const bool exp = a.hb_chk && (a.now - h[k]) > a.tte;
+            nq += (uint32_t)__popcll(__ballot(valid && !exp));
+            nqe += (uint32_t)__popcll(__ballot(valid && exp));
+            if (valid && !exp) disp += (unsigned long long)(f[k] > 1 ? f[k] : 1);
+        }
+        disp = wave_sum_u64(disp);
+        if (lane == 0) {
+            wv[wave][0] = nq;
+            wv[wave][1] = nqe;
+            wv[wave][2] = disp;
+        }
+        lds_barrier();
+        if (threadIdx.x < kPsQCols) {
+            unsigned long long v = 0;
+            if (threadIdx.x < 3)
+#pragma unroll
+                for (int w = 0; w < kWaves; ++w) v += wv[w][threadIdx.x];
+            a.qrow[(int64_t)qb * kPsQCols + threadIdx.x] = (int64_t)v;
+        }
+        return;
+    }
+    // slot role
+    hist[wave][lane] = 0;  // (a wave adds into its own row only)
+    const int s0 = bid * kPsSpan + (int)threadIdx.x;
+    uint8_t r[kPsTiles];
+    int32_t f[kPsTiles], b[kPsTiles];
+    double h[kPsTiles];
+#pragma unroll
+    for (int k = 0; k < kPsTiles; ++k) {
+        const int sc = s0 + k * kBS < a.W ? s0 + k * kBS : wlast;
+        r[k] = a.reg[sc];
+        f[k] = a.free_[sc].x;
+        h[k] = a.hb[sc];
+    }
+    if (a.bud) {
+#pragma unroll
+        for (int k = 0; k < kPsTiles; ++k) b[k] = a.bud[s0 + k * kBS < a.W ? s0 + k * kBS : wlast];
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPsTiles; ++k) b[k] = f[k];
+    }
+    uint32_t n_reg = 0, n_exp = 0, hn = 0, infl = 0;
+    unsigned long long fsum = 0;
+    double hmin = __builtin_huge_val(), hmax = -__builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < kPsTiles; ++k) {
+        const bool reg = s0 + k * kBS < a.W && r[k];
+        const double age = a.now - h[k];
+        const bool exp = a.hb_chk && reg && age > a.tte;
+        const bool alive = reg && !exp;
+        const unsigned long long mexp = __ballot(exp);
+        n_reg += (uint32_t)__popcll(__ballot(reg));
+        n_exp += (uint32_t)__popcll(mexp);
+        const int64_t word = ((int64_t)bid * kPsSpan + k * kBS + wave * 64) >> 6;
+        if (lane == 0 && word * 64 < a.W) a.xbits[word] = mexp;
+        if (alive) {
+            const int32_t fc = f[k] > 0 ? f[k] : 0;
+            fsum += (unsigned long long)fc;
+            atomicAdd(&hist[wave][fc < kPsFreeBins - 1 ? fc : kPsFreeBins - 1], 1u);
+            if (h[k] == h[k]) {
+                hmin = fmin(hmin, h[k]);
+                hmax = fmax(hmax, h[k]);
+                ++hn;
+            }
+        }
+        if (a.hb_chk && reg) {
+            int bin = 0;
+#pragma unroll
+            for (int e = 0; e < kPsMaxEdges; ++e) bin += (e < a.n_edges && age > a.edge[e]) ? 1 : 0;
+            atomicAdd(&hist[wave][kPsFreeBins + bin], 1u);
+        }
+        if (reg) {
+            const uint32_t in = (uint32_t)b[k] - (uint32_t)f[k];
+            infl = in > infl ? in : infl;
+        }
+    }
+    fsum = wave_sum_u64(fsum);
+    hn = wave_sum_u32(hn);
+    infl = wave_max_u32(infl);
+    hmin = wave_min_f64(hmin);
+    hmax = wave_max_f64(hmax);
+    if (lane < kPsFreeHist) {
+        unsigned long long v = 0;
+        v = lane == kPsReg ? n_reg : v;
+        v = lane == kPsExp ? n_exp : v;
+        v = lane == kPsFree ? fsum : v;
+        v = lane == kPsInflMax ? infl : v;
+        v = lane == kPsHbN ? hn : v;
+        v = lane == kPsHbMin ? (unsigned long long)__double_as_longlong(hmin) : v;
+        v = lane == kPsHbMax ? (unsigned long long)__double_as_longlong(hmax) : v;
+        wv[wave][lane] = v;
+    }
+    lds_barrier();
+    if (threadIdx.x < kPsCols) {
+        const int c = (int)threadIdx.x;
+        unsigned long long v = 0;
+        if (c < kPsFreeHist) {
+            v = ps_col_init(c);
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) v = ps_col_fold(c, v, wv[w][c]);
+        } else if (c < kPsUsed) {
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) v += hist[w][c - kPsFreeHist];
+        }
+        a.srow[(int64_t)bid * kPsCols + c] = (int64_t)v;
+    }
+}
+
+// A wave per tile as k_lc_flag; a live entry's slot is looked up in the expired bitmap
+// k_ps_slots wrote (hb_chk), the gathers branch-free at a clamped slot.
+__global__ __launch_bounds__(kBS) void k_ps_log(PsArgs a) {
+    prefetch_args(a);
+    __shared__ uint32_t wc[kWaves][kPsLCols];
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    const int lane = lane_id();
+    const int wlast = a.W > 0 ? a.W - 1 : 0;
+    const int64_t q0 = (int64_t)tile * kLcTile + lane;
+    uint32_t nl = 0, nle = 0;
+    if (tile < a.nt) {  // (the whole wave)
+        for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+            int32_t s[kLcBatch], sc[kLcBatch];
+            uint8_t r[kLcBatch];
+            uint32_t e[kLcBatch];
+            unsigned long long xw[kLcBatch];
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
+                s[k] = a.log[q < a.head ? q : a.head - 1];
+            }
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) sc[k] = s[k] < 0 ? 0 : (s[k] > wlast ? wlast : s[k]);
+            if (a.live_chk) {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) {
+                    r[k] = a.reg[sc[k]];
+                    e[k] = a.epoch[sc[k]];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) {
+                    r[k] = 1;
+                    e[k] = 0;
+                }
+            }
+            if (a.hb_chk) {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) xw[k] = a.xbits[sc[k] >> 6];
+            } else {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) xw[k] = 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
+                const bool live = q < a.head && s[k] >= 0 && r[k] && (uint64_t)q >= (uint64_t)e[k];
+                const bool exp = (xw[k] >> (sc[k] & 63)) & 1ull;
+                nl += (uint32_t)__popcll(__ballot(live && !exp));
+                nle += (uint32_t)__popcll(__ballot(live && exp));
+            }
+        }
+    }
+    if (lane == 0) {
+        wc[wave_id()][0] = nl;
+        wc[wave_id()][1] = nle;
+    }
+    lds_barrier();
+    if (threadIdx.x < kPsLCols) {
+        unsigned long long v = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) v += wc[w][threadIdx.x];
+        a.lrow[(int64_t)blockIdx.x * kPsLCols + threadIdx.x] = (int64_t)v;
+    }
+}
+
+// One workgroup: the slot rows a wave at a time (a lane per column, four rows' loads in
+// flight per wave), the narrow queue and log rows a thread per row; then the waves' partial
+// records through LDS into the result (host-mapped memory).
+__global__ __launch_bounds__(kPsFoldBS) void k_ps_fold(PsArgs a) {
+    prefetch_args(a);
+    constexpr int NW = kPsFoldBS / 64;
+    __shared__ unsigned long long part[NW][kPsCols];
+    const PsSlotsLayout lay = ps_slots_layout(a.W, a.Qn);
+    const int ns = lay.count(kPsSlotsSlots), nq = lay.count(kPsSlotsQueue), nl = quarter(a.nt);
+    const int lane = lane_id(), wave = wave_id();
+    unsigned long long acc = ps_col_init(lane);
+    for (int r0 = wave; r0 < ns; r0 += NW * 4) {
+        unsigned long long v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = r0 + k * NW;
+            v[k] = (unsigned long long)a.srow[(int64_t)(r < ns ? r : ns - 1) * kPsCols + lane];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (r0 + k * NW < ns) acc = ps_col_fold(lane, acc, v[k]);
+    }
+    unsigned long long t[5] = {0, 0, 0, 0, 0};
+    for (int r = (int)threadIdx.x; r < nq; r += kPsFoldBS) {
+        const longlong2 x = reinterpret_cast<const longlong2 *>(a.qrow)[2 * (int64_t)r];
+        const longlong2 y = reinterpret_cast<const longlong2 *>(a.qrow)[2 * (int64_t)r + 1];
+        t[0] += (unsigned long long)x.x;
+        t[1] += (unsigned long long)x.y;
+        t[2] += (unsigned long long)y.x;
+    }
+    for (int r = (int)threadIdx.x; r < nl; r += kPsFoldBS) {
+        const longlong2 x = reinterpret_cast<const longlong2 *>(a.lrow)[r];
+        t[3] += (unsigned long long)x.x;
+        t[4] += (unsigned long long)x.y;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) t[i] = wave_sum_u64(t[i]);
+    // (the slot rows hold 0 in these five columns)
+    acc = lane == kPsQ ? t[0] : acc;
+    acc = lane == kPsQExp ? t[1] : acc;
+    acc = lane == kPsDisp ? t[2] : acc;
+    acc = lane == kPsLive ? t[3] : acc;
+    acc = lane == kPsLiveExp ? t[4] : acc;
+    part[wave][lane] = acc;
+    lds_barrier();
+    if (threadIdx.x < kPsCols) {
+        const int c = (int)threadIdx.x;
+        unsigned long long v = ps_col_init(c);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v = ps_col_fold(c, v, part[w][c]);
+        a.out[c] = (int64_t)v;
+    }
+}
+
 }  // namespace fb
 
 // ------------------------------------------------------------ launchers
@@ -5268,6 +5567,18 @@ void launch_lc_scan(const LcArgs &a, Stream st) {
 void launch_lc_move(const LcArgs &a, Stream st) {
     const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
     if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lc_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_ps_slots(const PsArgs &a, Stream st) {
+    const PsPlan p = ps_plan(a.W, a.Qn, a.head);
+    if (p.slots.grid() > 0) hipExtLaunchKernelGGL(k_ps_slots, dim3(p.slots.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_ps_log(const PsArgs &a, Stream st) {
+    const PsPlan p = ps_plan(a.W, a.Qn, a.head);
+    if (p.log_grid > 0) hipExtLaunchKernelGGL(k_ps_log, dim3(p.log_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_ps_fold(const PsArgs &a, Stream st) {
+    const PsPlan p = ps_plan(a.W, a.Qn, a.head);
+    hipExtLaunchKernelGGL(k_ps_fold, dim3(p.fold_grid), dim3(kPsFoldBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_gate(uint32_t *flag, uint32_t want, uint64_t limit, Stream st) {
     hipExtLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st.s, st.e0, st.e1, 0, flag, want, limit);

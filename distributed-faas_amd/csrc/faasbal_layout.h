@@ -305,6 +305,67 @@ inline LcPlan lc_plan(int64_t head, int W, bool want_kept) {
 }
 
 // ---------------------------------------------------------------------------------------
+// fb_pool_stats: three launches, none of which writes anything but the scratch.
+//   k_ps_slots  slot workgroups (kPsTiles tiles of kBS slots each: the counts, sums, minima
+//               and histograms of a row of kPsCols words, and the expired bitmap, a 64-bit
+//               word per wave and tile), then queue workgroups (kPsTiles tiles of kBS
+//               positions of the window [qoff, qoff + Qn): a row of kPsQCols words)
+//   k_ps_log    a wave per kLcTile-entry tile, four per workgroup: a row of kPsLCols words
+//   k_ps_fold   one workgroup of kPsFoldBS threads: the rows folded into the record
+// Every workgroup writes its whole row, so the scratch needs no clearing.  ps_plan states the
+// grids and the scratch's regions (256-byte aligned byte offsets) for W slots, a window of
+// Qn positions and a log of `head` entries (tests/ps_probe.cpp walks it on the CPU).
+constexpr int kPsTiles = 4;
+constexpr int kPsSpan = kPsTiles * kBS;  // slots / positions per workgroup
+constexpr int kPsFreeBins = 33, kPsAgeBins = kPsMaxEdges + 1;
+// columns of a slot row and of the folded record (sums, but for the three marked)
+enum {
+    kPsReg, kPsExp, kPsQ, kPsQExp, kPsDisp, kPsFree, kPsLive, kPsLiveExp,
+    kPsInflMax,          // maximum (unsigned)
+    kPsHbN,              // heartbeats that went into the minimum and the maximum
+    kPsHbMin, kPsHbMax,  // doubles' bit patterns: minimum (from +inf), maximum (from -inf)
+    kPsFreeHist,
+    kPsAgeHist = kPsFreeHist + kPsFreeBins,
+    kPsUsed = kPsAgeHist + kPsAgeBins
+};
+constexpr int kPsCols = 64;
+static_assert(kPsUsed <= kPsCols, "a row is one 64-lane wave load");
+constexpr int kPsQCols = 4;  // a queue row: queued, queued on expired slots, dispatchable, 0
+constexpr int kPsLCols = 2;  // a log row: live entries on slots not expired, on expired slots
+constexpr int kPsFoldBS = 1024;
+enum { kPsSlotsSlots, kPsSlotsQueue };
+struct PsSlotsLayout : Roles<2> {};
+FB_HD PsSlotsLayout ps_slots_layout(int W, int64_t Qn) { return {{{(int)cdiv(W, kPsSpan), (int)cdiv(Qn, kPsSpan)}}}; }
+struct PsPlan {
+    int nt;        // log tiles
+    int64_t nxw;   // expired bitmap words
+    PsSlotsLayout slots;
+    int log_grid, fold_grid;
+    size_t xbits, srow, qrow, lrow;  // regions: nxw x 8, slot wgs x kPsCols x 8, queue wgs x kPsQCols x 8, log wgs x kPsLCols x 8 bytes
+    size_t bytes;
+};
+inline PsPlan ps_plan(int W, int64_t Qn, int64_t head) {
+    PsPlan p{};
+    p.nt = (int)cdiv(head, kLcTile);
+    p.nxw = cdiv(W, 64);
+    p.slots = ps_slots_layout(W, Qn);
+    p.log_grid = quarter(p.nt);
+    p.fold_grid = 1;
+    size_t o = 0;
+    auto take = [&o](size_t b) {
+        const size_t at = o;
+        o += (b + 255) & ~(size_t)255;
+        return at;
+    };
+    p.xbits = take((size_t)(p.nxw > 0 ? p.nxw : 1) * 8);  // (word 0 is read, and masked, by a log without slots)
+    p.srow = take((size_t)p.slots.count(kPsSlotsSlots) * kPsCols * 8);
+    p.qrow = take((size_t)p.slots.count(kPsSlotsQueue) * kPsQCols * 8);
+    p.lrow = take((size_t)p.log_grid * kPsLCols * 8);
+    p.bytes = o;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------
 // The died bitmap (a bit per slot, 64-bit words) staged in dynamic LDS by whole int4: the
 // bytes a launch requests and the int4 count the kernel's copy loops over.
 struct BitmapLds {

@@ -28,7 +28,7 @@ EXPORTS = ("fb_create", "fb_destroy", "fb_last_error", "fb_load_state", "fb_read
            "fb_read_inflight", "fb_set_compact", "fb_get_outputs_compact", "fb_expand_compact",
            "fb_set_window", "fb_window_stats", "fb_set_compact_out", "fb_set_eager_commit", "fb_set_path",
            "fb_set_round_hint", "fb_set_full_assign", "fb_timing_gate", "fb_timing_span",
-           "fb_timing_mark", "fb_log_compact")
+           "fb_timing_mark", "fb_log_compact", "fb_pool_stats")
 
 
 class TickResult(C.Structure):
@@ -39,6 +39,18 @@ class TickResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+PS_FREE_BINS, PS_MAX_EDGES = 33, 15  # FB_PS_FREE_BINS, FB_PS_MAX_EDGES
+
+
+class PoolSummary(C.Structure):
+    """fb_pool_summary."""
+    _fields_ = [(k, C.c_int64) for k in ("n_slots", "n_registered", "n_expired", "n_queued", "n_queued_expired",
+                                          "dispatchable", "free_total", "log_head", "inflight",
+                                          "inflight_expired", "inflight_max")] + \
+               [("oldest_hb", C.c_double), ("newest_hb", C.c_double),
+                ("free_hist", C.c_int64 * PS_FREE_BINS), ("age_hist", C.c_int64 * (PS_MAX_EDGES + 1))]
 
 
 class DeviceView(C.Structure):
@@ -128,6 +140,7 @@ def load(path=None):
         "fb_purge_launch": (C.c_int, [_P, dbl, dbl]),
         "fb_read_inflight": (C.c_int, [_P, _P]),
         "fb_log_compact": (C.c_int, [_P, i64, _P, i64, C.POINTER(i64)]),
+        "fb_pool_stats": (C.c_int, [_P, dbl, dbl, _P, C.c_int32, C.POINTER(PoolSummary)]),
         "fb_set_compact": (C.c_int, [_P, C.c_int]),
         "fb_set_window": (C.c_int, [_P, C.c_int]),
         "fb_set_eager_commit": (C.c_int, [_P, C.c_int]),

@@ -259,6 +259,20 @@ class GpuBalancer:
                                           kept.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return {"n_kept": n.value, "kept": kept[: n.value]}
 
+    def pool_stats(self, now, tte, age_edges=()):
+        """fb_pool_stats: the committed pool summarised on the device at the clock ``now``
+        (expired = registered and ``(now - hb) > tte``, the tick's test): a dict of
+        fb_pool_summary's scalars as Python numbers and ``free_hist`` / ``age_hist`` as int64
+        arrays (``age_edges``: up to 15 ascending ages).  Reads only -- no state read, no log
+        settle; the tick pipeline stays as it is.  Between ticks, not with staged events."""
+        edges = _arr(age_edges, np.float64).reshape(-1)
+        out = _lib.PoolSummary()
+        self._chk(self.lib.fb_pool_stats(self.h, float(now), float(tte), _p(edges), len(edges), C.byref(out)))
+        d = {k: getattr(out, k) for k, _ in out._fields_[:-2]}
+        d["free_hist"] = np.array(out.free_hist, np.int64)
+        d["age_hist"] = np.array(out.age_hist, np.int64)
+        return d
+
     # ----------------------------------------------------------------- ticks
     def launch(self, now, tte, ev_kind=(), ev_slot=(), ev_val=(), ev_ts=(), ev_seq=None, n_pending=0):
         if not len(ev_kind) and not len(ev_slot):

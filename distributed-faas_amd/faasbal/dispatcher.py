@@ -39,6 +39,8 @@ class without a GPU fails loudly.
 from __future__ import annotations
 
 import collections
+import json
+import math
 import time
 
 import numpy as np
@@ -46,6 +48,7 @@ import numpy as np
 from . import codec
 from ._lib import FB_ENOSPC, FB_ESTATE, FB_EVS_RECONNECT, FaasbalError
 from .balancer import GpuBalancer
+from .poolstats import pool_stats_model
 
 EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER = 0, 1, 2, 3, 4
 _KINDS = {"register": EV_REGISTER, "reconnect": EV_RECONNECT, "heartbeat": EV_HEARTBEAT, "result": EV_RESULT}
@@ -121,6 +124,7 @@ class GpuPushDispatcher:
         self.ticks = 0
         self.compactions = 0
         self.device_compactions = 0                    # ... of which on the device (fb_log_compact)
+        self.stats_every = 0                           # N > 0: publish_stats() after every N-th tick (0: never)
 
     @classmethod
     def subclass_of(cls, base):
@@ -403,6 +407,8 @@ class GpuPushDispatcher:
         for s in out["evicted"]:
             self._release(int(s))
         self.ticks += 1
+        if self.stats_every > 0 and self.ticks % self.stats_every == 0:
+            self.publish_stats()
         return res
 
     def start_heartbeat(self, max_ticks=None):
@@ -451,6 +457,42 @@ class GpuPushDispatcher:
         identities possibly repeated) as a list of identities, front first."""
         st = self.balancer.read_state(with_log=False)
         return [self.identity[s] for s in st["queue"]]
+
+    def pool_stats(self, age_edges=None):
+        """The state of the worker pool at the current clock, between ticks: the fields of
+        fb_pool_summary (include/faasbal.h) -- registered / expired / queued workers, the
+        tasks the next tick could place (``dispatchable``), live in-flight tasks and those
+        sitting on expired workers, heartbeat range, histograms of free processes and of
+        heartbeat age (``age_edges``, default a quarter, half, three quarters and the whole of
+        ``time_to_expire``) -- plus the host's own figures: ``pending``, ``inflight_host``,
+        ``ticks``, ``compactions`` and ``log_garbage`` (log entries that are not live).  A
+        balancer with ``pool_stats`` (a one-GPU ``GpuBalancer``: fb_pool_stats) computes it on
+        the device, a few hundred bytes back and the tick pipeline untouched; otherwise (shard
+        groups) the whole state is read and summarised by ``faasbal.poolstats``."""
+        tte = float(self.time_to_expire)
+        if age_edges is None:
+            age_edges = tuple(tte * f for f in (0.25, 0.5, 0.75, 1.0))
+        now = self._stamp()
+        device = getattr(self.balancer, "pool_stats", None)
+        if callable(device):
+            s = dict(device(now, tte, age_edges))
+        else:
+            s = pool_stats_model(self.balancer.read_state(with_log=True), now, tte, age_edges,
+                                 deque=self.mode == "deque")
+        s.update(now=now, pending=len(self.pending), inflight_host=len(self.inflight), ticks=self.ticks,
+                 compactions=self.compactions,
+                 log_garbage=s["log_head"] - s["inflight"] - s["inflight_expired"])
+        return s
+
+    def publish_stats(self, key="faasbal:pool"):
+        """HSET ``key`` {summary: pool_stats() as JSON, ts: its clock} for the gateway's
+        ``GET /pool`` (NaN, which JSON lacks, as null).  ``stats_every = N`` makes the loop
+        call this after every N-th tick; by default (0) it never does."""
+        s = self.pool_stats()
+        doc = {k: (v.tolist() if isinstance(v, np.ndarray) else
+                   None if isinstance(v, float) and math.isnan(v) else v) for k, v in s.items()}
+        self.redis_client.hset(key, mapping={"summary": json.dumps(doc), "ts": repr(s["now"])})
+        return s
 
     def compact_log(self):
         """Renumber the in-flight log densely (completed and redistributed entries

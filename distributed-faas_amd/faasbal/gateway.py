@@ -26,6 +26,7 @@ publish pipelined).
 """
 
 import collections
+import json
 import threading
 import uuid
 
@@ -204,9 +205,21 @@ class Gateway:
             return None
         return {"task_id": task_id, "status": _s(h[b"status"]), "result": _s(h.get(b"result", b"None"))}
 
+    def pool(self, key="faasbal:pool"):
+        """The worker pool's summary as the dispatcher last published it
+        (``GpuPushDispatcher.publish_stats``) plus ``ts``, its clock then; None while no
+        dispatcher has published.  (Not one of the reference clients' calls: the reference
+        keeps no such view.)"""
+        h = self.r.hgetall(key)
+        if not h or b"summary" not in h:
+            return None
+        out = json.loads(_s(h[b"summary"]))
+        out["ts"] = float(_s(h.get(b"ts", b"nan")))
+        return out
+
 
 def create_app(redis_client=None, tasks_channel="tasks"):
-    """FastAPI app with the four endpoints the reference's clients call."""
+    """FastAPI app with the four endpoints the reference's clients call, and ``GET /pool``."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -245,6 +258,13 @@ def create_app(redis_client=None, tasks_channel="tasks"):
         out = gw.result(task_id)
         if out is None:
             raise HTTPException(status_code=404, detail="unknown task_id %s" % task_id)
+        return out
+
+    @app.get("/pool")
+    def pool():
+        out = gw.pool()
+        if out is None:
+            raise HTTPException(status_code=404, detail="no dispatcher has published a pool summary")
         return out
 
     return app

@@ -81,6 +81,9 @@ class ShardedBalancer(GpuBalancer):
 
     # fb_log_compact refuses sharded contexts (sequence numbers are global across ranks)
     compact_log = None
+    # fb_pool_stats too (the pool is the group's: a summary needs a collective); shard groups
+    # take GpuPushDispatcher.pool_stats' host path
+    pool_stats = None
 
     def load(self, st):
         """Load this rank's part of a global state dict."""

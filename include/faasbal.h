@@ -120,6 +120,47 @@ int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
  * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
 int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept);
 
+/* One-GPU contexts (heartbeat and deque), between ticks: a summary of the committed worker pool
+ * at the clock `now`, computed where the state lives (three launches, a few hundred bytes back;
+ * DESIGN.md §5e).  A slot is expired iff it is registered and (now - last_heartbeat) > tte, the
+ * tick's own test, so n_expired / inflight_expired / dispatchable are what a tick at the same
+ * (now, tte) without messages evicts / redistributes / can place.  A log entry is live by
+ * fb_log_compact's rule.  The call reads only: the committed state, the log's lazily kept
+ * entries included, and the tick pipeline (window, queue buffers, round hints) stay as they are.
+ * age_edges: n_edges (0 .. FB_PS_MAX_EDGES) finite, strictly ascending ages for age_hist.
+ * Deque contexts have no liveness: now, tte and the edge values are ignored, n_expired,
+ * n_queued_expired and inflight_expired are 0, age_hist is all zero, oldest_hb and newest_hb
+ * are NaN, dispatchable is -1, and n_queued counts tokens with repetition.
+ * FB_EINVAL: out == NULL, n_edges outside [0, FB_PS_MAX_EDGES], and on heartbeat contexts edges
+ * not finite and strictly ascending or a non-finite now or tte.  FB_ESTATE: a sharded context
+ * (its pool is the group's, which needs a collective), staged events pending, a tick launched
+ * but not committed.  A refused call changes nothing.
+ * Replaces nothing in the reference, which keeps no such view: its only look at the pool is
+ * the per-worker is_alive walk of purge_workers (task_dispatcher.py:241-249). */
+#define FB_PS_FREE_BINS 33
+#define FB_PS_MAX_EDGES 15
+typedef struct fb_pool_summary {
+    int64_t n_slots, n_registered;
+    int64_t n_expired;        /* registered and (now - hb) > tte: what a purge at `now` evicts   */
+    int64_t n_queued;         /* queue positions (tombstones excluded) whose slot is not expired */
+    int64_t n_queued_expired; /* ... whose slot is expired; the two sum to the queue length      */
+    int64_t dispatchable;     /* sum of max(free, 1) over the n_queued positions = the tick's
+                                 Sigma c; -1 on deque contexts                  */
+    int64_t free_total;       /* sum of max(free, 0) over registered, not expired slots          */
+    int64_t log_head;
+    int64_t inflight;         /* live log entries on slots that are not expired                  */
+    int64_t inflight_expired; /* live log entries on expired slots = the orphans of a purge now  */
+    int64_t inflight_max;     /* contexts with in-flight counts (fb_read_inflight): the largest
+                                 per-slot count over registered slots; else -1                   */
+    double oldest_hb, newest_hb; /* min / max heartbeat over registered, not expired slots,
+                                 NaN heartbeats skipped; NaN when there is none                  */
+    int64_t free_hist[FB_PS_FREE_BINS]; /* registered, not expired: bin clamp(free, 0, 32)       */
+    int64_t age_hist[FB_PS_MAX_EDGES + 1]; /* registered: bin = number of edges e with
+                                 (now - hb) > e                                                  */
+} fb_pool_summary;
+int fb_pool_stats(fb_ctx *ctx, double now, double tte, const double *age_edges, int32_t n_edges,
+                  fb_pool_summary *out);
+
 /* Enqueue one tick on the context's stream (no host sync).
  * Replaces, per tick: the inbound branches (task_dispatcher.py:343-387), the
  * purge (:241-249, called at :390) and the dispatch block (:393-419), plus the
