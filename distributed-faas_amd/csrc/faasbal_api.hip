@@ -308,13 +308,16 @@ struct fb_ctx {
     bool xz_ok = false;
     int phase = 0;                                    // 1: phase 1 enqueued; 2: phase 2 enqueued
     int shard_R = 0;                                  // > 0: round rows a relaunch asked for (FB_ERERUN)
-    // sharded: results clear their log entries in place at launch; the entries a launch
-    // cleared (per message, tagged with the launch's stamp) are named again by the next
-    // launch unless the tick was committed in between
+    // contexts without deferred clears (sharded, deque, one GPU past kLdsBitmapSlots): results
+    // clear their log entries in place at launch; the entries a launch cleared (per message,
+    // tagged per fb_tick_launch: fb_tick_wait's reruns write under the same tag) are named
+    // again -- log_undo -- by the next launch, or by a reader of the committed state once the
+    // launch's wait has failed, unless the tick was committed in between
     int64_t *undo_idx = nullptr;
     unsigned long long *undo_key = nullptr;
-    uint32_t undo_tag = 0;
+    uint32_t undo_tag = 0;                            // the last host launch's tag (never 0)
     int undo_E = 0;                                   // > 0: messages of a launch not committed yet
+    bool l_failed = false;                            // the launched tick's fb_tick_wait failed: it never commits
     hipStream_t own_s = nullptr;                      // the context's own stream (fb_set_stream may borrow another)
 };
 
@@ -646,6 +649,32 @@ int log_settle(fb_ctx *c) {
     return FB_OK;
 }
 
+// The in-place clears of a launch that was never committed, taken back: the log entries its
+// results completed are in flight again.  (Before the next launch, and before anything reads
+// or replaces the committed log once the launch's wait has failed -- log_undo_failed; between
+// a successful wait and the commit the clears stay: the commit relies on them.)
+int log_undo(fb_ctx *c) {
+    if (c->undo_E <= 0) return FB_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    {
+        Timer t(c, "log_undo");
+        launch_log_undo(c->log_slot, c->undo_idx, c->undo_key, c->undo_tag, c->undo_E, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    c->undo_E = 0;
+    return FB_OK;
+}
+
+// sync: the caller hands the log to a reader outside the context's stream
+int log_undo_failed(fb_ctx *c, bool sync = false) {
+    // (a launch still waiting to be waited for or committed keeps its clears; every failed
+    // wait sets l_failed, whether or not it also cleared `launched`)
+    if (c->undo_E <= 0 || !c->l_failed) return FB_OK;
+    if (int rc_ = log_undo(c)) return rc_;
+    if (sync) HIPCHK(c, stream_wait(c));
+    return FB_OK;
+}
+
 // Whether the tick about to launch (c->l_*) runs as a window tick: plan_window's rules on
 // this context's state; c->l_nchW, the window chunks it scans.
 bool win_plan(fb_ctx *c) {
@@ -759,7 +788,7 @@ EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const
     ea.post_infl = c->post_infl;
     ea.undo_idx = c->undo_idx;
     ea.undo_key = c->undo_key;
-    ea.undo_tag = c->lstamp;
+    ea.undo_tag = c->undo_tag;
     if (p.grouping == Grouping::sort) {
         ea.deque = c->deque;
         ea.tokcnt_in = c->tokcnt[cur];
@@ -1357,6 +1386,9 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
         ap.add(&c->xg_tk, ng);
         ap.add(&c->xs_tk, (size_t)64);  // k_xscan's ticket (zero: the arena is zeroed, the last workgroup resets it)
         ap.add(&c->ogrp, ng * kXGroupR);
+    }
+    // every context that clears in place (no bud / ctag above) notes its clears (k_log_undo)
+    if (shard || c->deque || W > (size_t)kLdsBitmapSlots) {
         ap.add(&c->undo_idx, E);
         ap.add(&c->undo_key, E);
     }
@@ -1581,6 +1613,7 @@ int fb_load_state(fb_ctx *c, int32_t n_workers, const uint8_t *registered, const
     c->last_L = -1;
     c->last_O = 0;
     c->launched = c->waited = false;
+    c->undo_E = 0;  // an abandoned launch's notes name entries of the log this one replaced
     return FB_OK;
 }
 
@@ -1589,6 +1622,7 @@ int fb_read_state(fb_ctx *c, uint8_t *registered, int32_t *free_processes, doubl
     if (!c) return FB_EINVAL;
     if (int rc_ = win_uncommitted(c, "fb_read_state")) return rc_;
     if (int rc_ = flush_commit(c)) return rc_;
+    if (int rc_ = log_undo_failed(c)) return rc_;  // a failed launch's in-place clears
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, stream_wait(c));
     const size_t W = (size_t)c->W;
@@ -1749,6 +1783,8 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     if (c->launched && (!c->l_enospc || c->l_win))
         return fail(c, FB_ESTATE, "fb_log_compact with a tick launched: fb_tick_wait and fb_tick_commit first");
     if (int rc_ = flush_commit(c)) return rc_;
+    // the discarded tick's results completed nothing: its clears are taken back before the count
+    if (int rc_ = log_undo_failed(c)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     const LcPlan p = lc_plan(c->head, c->W, kept_seq != nullptr);
     if (p.bytes > c->lc_cap) {
@@ -1811,6 +1847,7 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     c->head = (int64_t)live;
     c->stale_any = false;  // a compacted log holds only live entries
     c->launched = c->waited = false;  // (the discarded FB_ENOSPC tick)
+    c->undo_E = 0;  // (notes name the old numbering)
     c->l_enospc = false;
     if (n_kept) *n_kept = (int64_t)live;
     return FB_OK;
@@ -1842,6 +1879,7 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     if (c->launched)
         return fail(c, FB_ESTATE, "fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first");
     if (int rc_ = flush_commit(c)) return rc_;  // (observably an immediate commit)
+    if (int rc_ = log_undo_failed(c)) return rc_;  // a failed launch's in-place clears
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->ps_out) {
         if (hipHostMalloc((void **)&c->ps_out, kPsCols * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
@@ -2255,22 +2293,16 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     c->hout->new_qlen = -1;
     c->hout->win_head = -1;
     c->hout->win_qlen = -1;
-    if (c->undo_E > 0) {
-        // the last launch was never committed (abandoned, failed, or asked for this relaunch):
-        // the log entries its results completed are in flight again
-        {
-            Timer t(c, "log_undo");
-            launch_log_undo(c->log_slot, c->undo_idx, c->undo_key, c->undo_tag, c->undo_E, t.st());
-        }
-        HIPCHK(c, hipGetLastError());
-        c->undo_E = 0;
-    }
-    const uint32_t stamp0 = c->lstamp;
-    const int rc = enqueue_tick(c);
-    if (c->undo_idx && c->lstamp != stamp0) {  // (phase 1 was enqueued under a stamp of its own)
+    // the last launch was never committed (abandoned, failed, or asked for this relaunch)
+    if (int rc_ = log_undo(c)) return rc_;
+    c->l_failed = false;
+    if (c->undo_idx) {
+        // one tag per host launch: the notes of fb_tick_wait's reruns and of a sharded
+        // tick's phase 2 belong to this launch too (notes under older tags are never applied)
+        if (++c->undo_tag == 0) c->undo_tag = 1;
         c->undo_E = E;
-        c->undo_tag = c->lstamp;
     }
+    const int rc = enqueue_tick(c);
     if (rc) return rc;
     c->l_eager = false;
     if (c->eager && c->l_win) {
@@ -2346,10 +2378,20 @@ static int check_lengths(fb_ctx *c) {
     return FB_OK;
 }
 
+static int tick_wait(fb_ctx *c, fb_tick_result *res);
+
 int fb_tick_wait(fb_ctx *c, fb_tick_result *res) {
     if (!c) return FB_EINVAL;
     if (!c->launched) return fail(c, FB_ESTATE, "fb_tick_wait without fb_tick_launch");
     if (c->shard && c->phase != 2) return fail(c, FB_ESTATE, "sharded tick: exchange, then fb_tick_continue");
+    const int rc = tick_wait(c, res);
+    // whatever failed, this launch never commits: a reader of the committed state takes its
+    // in-place clears back (log_undo_failed) without waiting for the next launch
+    if (rc) c->l_failed = true;
+    return rc;
+}
+
+static int tick_wait(fb_ctx *c, fb_tick_result *res) {
     HIPCHK(c, hipSetDevice(c->device));
     for (bool first = true;; first = false) {
         if (first && c->l_eager) {
@@ -2989,6 +3031,7 @@ int fb_device_view_get(fb_ctx *c, fb_device_view *v) {
     if (!c || !v) return FB_EINVAL;
     if (int rc_ = win_uncommitted(c, "fb_device_view_get")) return rc_;
     if (int rc_ = flush_commit(c)) return rc_;
+    if (int rc_ = log_undo_failed(c, true)) return rc_;  // a failed launch's in-place clears
     v->free_processes = &c->free_[c->cur]->x;
     v->free_processes_stride = (int32_t)sizeof(int2);
     v->last_heartbeat = c->hb;

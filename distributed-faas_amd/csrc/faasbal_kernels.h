@@ -249,9 +249,10 @@ struct EvArgs {
     int slot_base, W;
     int64_t head_local; // sharded: local log length (entries carry their global seq in lseq)
     const uint32_t *lseq;
-    // sharded: a result clears its log entry in place; message i notes the entry it cleared
-    // and {this launch's tag, slot}, so the next launch can take back an abandoned launch's
-    // clears (k_log_undo).  Null elsewhere
+    // contexts without deferred clears (sharded, deque, one GPU past kLdsBitmapSlots): a
+    // result clears its log entry in place; message i notes the entry it cleared and {the
+    // host launch's tag -- its reruns keep it --, slot}, so an abandoned or failed launch's
+    // clears can be taken back (k_log_undo).  Null on contexts that defer their clears
     int64_t *undo_idx;
     unsigned long long *undo_key;
     uint32_t undo_tag;

@@ -617,7 +617,14 @@ __device__ void ev_apply_deque(const EvArgs &a, int j, uint32_t s) {
             } else {
                 fr += 1;
                 const int64_t q = a.ev_seq[i];
-                if (q >= 0 && q < a.head_in && a.log_slot[q] == (int32_t)s) a.log_slot[q] = -1;
+                if (q >= 0 && q < a.head_in && a.log_slot[q] == (int32_t)s) {
+                    // cleared in place, and noted for k_log_undo should the launch be abandoned
+                    a.log_slot[q] = -1;
+                    if (a.undo_idx) {
+                        a.undo_idx[i] = q;
+                        a.undo_key[i] = ((unsigned long long)a.undo_tag << 32) | s;
+                    }
+                }
                 if (fr == 1) {
                     ++nb;
                     a.back_list[i] = (int32_t)s + 1;
@@ -704,11 +711,19 @@ struct SlotRun {
                 if (PF) {
                     // one GPU: the entry's slot loaded ahead.  defer_clr: the log stays as
                     // committed (the commit clears the entry), ctag names the entry for this
-                    // launch; else cleared in place (clearing it twice is harmless)
+                    // launch; else cleared in place (clearing it twice is harmless) and noted
+                    // for k_log_undo should the launch be abandoned
                     if (logv == (int32_t)gs && !dup) {
                         cleared = true;
-                        if (a.defer_clr) a.ctag[q] = a.lstamp;
-                        else a.log_slot[q] = -1;
+                        if (a.defer_clr) {
+                            a.ctag[q] = a.lstamp;
+                        } else {
+                            a.log_slot[q] = -1;
+                            if (a.undo_idx) {
+                                a.undo_idx[i] = q;
+                                a.undo_key[i] = ((unsigned long long)a.undo_tag << 32) | gs;
+                            }
+                        }
                     }
                 } else if (a.defer_clr) {
                     // sorted path, one GPU: a slot may carry any number of results; the
@@ -718,8 +733,9 @@ struct SlotRun {
                     const int64_t li = a.shard ? lseq_find(a.lseq, a.head_local, q) : q;
                     if (li >= 0 && a.log_slot[li] == (int32_t)gs) {
                         a.log_slot[li] = -1;
-                        // sharded: cleared in place (this tick's log scan reads it), and noted
-                        // for k_log_undo should the launch be abandoned
+                        // sharded, and the sorted path of one-GPU contexts past kLdsBitmapSlots:
+                        // cleared in place (sharded: this tick's log scan reads it), and noted for
+                        // k_log_undo should the launch be abandoned
                         if (a.undo_idx) {
                             a.undo_idx[i] = li;
                             a.undo_key[i] = ((unsigned long long)a.undo_tag << 32) | gs;

@@ -262,13 +262,14 @@ class GpuPushDispatcher:
         results (kept out of the table, their HSET done here)."""
         keep, unknown = [], []
         known = set(self.slot_of)
-        for wid, m, t in msgs:
+        for x in msgs:  # (the tuples themselves: _run finds a message's batch index by identity)
+            wid, m, _t = x
             typ = m.get("type") if isinstance(m, dict) else None
             if typ == "register":
                 known.add(wid)
-                keep.append((wid, m, t))
+                keep.append(x)
             elif typ == "result":
-                (keep if wid in known else unknown).append((wid, m, t))
+                (keep if wid in known else unknown).append(x)
         return keep, unknown
 
     def _run(self, msgs):

@@ -93,7 +93,10 @@ int fb_load_state(fb_ctx *ctx, int32_t n_workers, const uint8_t *registered,
                   const uint32_t *epoch, const int32_t *queue, int64_t queue_len,
                   const int32_t *log_slot, int64_t log_len);
 
-/* Read the committed state back (any pointer may be NULL). */
+/* Read the committed state back (any pointer may be NULL).  Between a successful
+ * fb_tick_wait and its fb_tick_commit, a context that completes log entries in place
+ * (deque, sharded, one GPU with more than 128 K workers; see fb_tick_launch) shows the
+ * log with the entries the launched tick's results completed already at -1. */
 int fb_read_state(fb_ctx *ctx, uint8_t *registered, int32_t *free_processes,
                   double *last_heartbeat, uint32_t *epoch, int32_t *queue, int64_t *queue_len,
                   int32_t *log_slot, int64_t *log_len);
@@ -116,7 +119,9 @@ int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
  * FB_ESTATE also: a sharded context (its sequence numbers are global across ranks: compacting
  * them needs a collective), staged events pending, a tick launched but not waited, or waited
  * but not committed.  A tick whose fb_tick_wait failed with FB_ENOSPC is discarded (launch it
- * again with the new sequences), as fb_load_state discards it.
+ * again with the new sequences), as fb_load_state discards it: on every context kind the
+ * entries its results named count as live and are kept (a context that completed them in
+ * place at launch names them again before it counts).
  * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
 int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept);
 
@@ -169,9 +174,15 @@ int fb_pool_stats(fb_ctx *ctx, double now, double tte, const double *age_edges, 
  * n_pending = tasks waiting in pub/sub (carried-over ones first).
  * Reads the committed state, writes the tick's outputs and the next state into
  * separate buffers: launching again without fb_tick_commit recomputes the same
- * tick (used by the benchmark).  Sharded contexts clear the log entries that results
- * complete in place; a launch after a tick that was never committed first restores
- * them, so it may carry other messages. */
+ * tick (used by the benchmark), and the next launch may carry other messages.  This holds
+ * on every context kind.  One-GPU heartbeat contexts of at most 128 K workers leave the log
+ * untouched until the commit.  The others (deque, sharded, one GPU with more workers) set
+ * the log entries that results complete to -1 in place, at launch, and note them: the
+ * next launch first names them again unless the tick was committed, and so does, once a
+ * tick's fb_tick_wait has failed (FB_ENOSPC, an invalid message, a refused length), the
+ * first call that reads or replaces the committed log (fb_read_state, fb_log_compact,
+ * fb_pool_stats, fb_device_view_get).  fb_load_state / fb_load_shard drop the notes with
+ * the log they replace. */
 int fb_tick_launch(fb_ctx *ctx, double now, double tte, int32_t n_events, const uint8_t *kind,
                    const int32_t *slot, const int32_t *val, const double *ts, const int64_t *seq,
                    int64_t n_pending);

@@ -505,6 +505,36 @@ def test_dispatcher_start_unknown_result_does_not_kill_the_loop(dispatcher_cls):
     assert b"ghost" not in d.workers
 
 
+def test_dispatcher_start_results_leave_the_inflight_table(dispatcher_cls):
+    """Regression: the loop without heartbeats filtered its messages into new tuples, so _run
+    (which finds a message's batch index by identity) took every result for one of an
+    unknown identity: the HSET was done, but the task stayed in the in-flight table for ever,
+    which then disagreed with the device log (compact_log fell back to its host path and
+    put the finished entries back).  The table is the device log after every tick."""
+    env = FakeEnv()
+    d = dispatcher_cls("127.0.0.1", 0, 10, max_workers=8, max_events=16, max_inflight=64,
+                       redis_client=env, subscriber=env, socket=env, poller=env, clock=env.clock)
+    d.use_loop("deque")
+    env.inbound.append((wid(0), codec.serialize({"type": "register", "data": {"num_processes": 1}}).encode(), 0.0))
+    env.inbound.append((wid(1), codec.serialize({"type": "register", "data": {"num_processes": 2}}).encode(), 0.0))
+    env.tasks.extend("t%d" % j for j in range(6))
+    for t in range(3):
+        for dst, m in list(env.sent):
+            if m["type"] == "task" and dst == wid(0):
+                env.inbound.append((dst, codec.serialize({"type": "result", "data": {
+                    "task_id": m["data"]["task_id"], "status": "COMPLETED", "result": 1}}).encode(), float(t)))
+        env.sent.clear()
+        d.tick()
+        want = np.full(d.head, -1, np.int32)
+        for q, (_tid, s) in d.inflight.items():
+            want[q] = s
+        np.testing.assert_array_equal(d.balancer.read_state()["log"], want, err_msg="tick %d" % t)
+    # worker 0 finished two tasks and holds its third, worker 1 holds two and never answered
+    s0, s1 = d.slot_of[wid(0)], d.slot_of[wid(1)]
+    assert sorted(s for _, s in d.inflight.values()) == sorted([s0, s1, s1]) and len(env.hsets) == 5 + 2
+    assert d.task_seq == {tid: q for q, (tid, _) in d.inflight.items()}
+
+
 def test_batched_io_round_trips(dispatcher_cls):
     """Pipelined host I/O: 2 Redis round trips for a tick's dispatches (+1 for its
     results) instead of 3 per task (+1 per result); same messages and writes."""
