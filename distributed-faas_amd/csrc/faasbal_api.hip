@@ -21,6 +21,7 @@
 
 #include "faasbal.h"
 #include "faasbal_kernels.h"
+#include "faasbal_life.h"
 #include "faasbal_plan.h"
 
 using namespace fb;
@@ -144,8 +145,7 @@ struct fb_ctx {
     int64_t qoff = 0, qcap = 0, Qtrue = 0;  // Qtrue: the LRU queue's length (tombstones excluded)
     bool win_cap = false;      // the context can run window ticks (buffers allocated)
     int win = -1;              // fb_set_window: -1 auto (large tables), 0 off, 1 on
-    bool l_win = false;        // the last launch is a window tick
-    int l_nchW = 0;            // ... and the window chunks it scans
+    int l_nchW = 0;            // the window chunks the last launch scans (a window tick: life.win)
     int64_t l_qoff = 0;
     int32_t *pos_of[2] = {nullptr, nullptr};
     bool pos_ok = false;       // pos_of[qcur] is exact for every queued slot (general ticks do not keep it)
@@ -172,10 +172,9 @@ struct fb_ctx {
     uint32_t *tbitsb[2] = {nullptr, nullptr};  // by launch parity: a deferred commit reads the last tick's
     // fb_tick_commit of a one-GPU heartbeat context is deferred into the next launch's
     // k_ev_link (extra blocks) or flushed as its own launch by the next call that needs it
-    bool cm_pending = false;
+    // (life.cm_pending)
     CommitArgs cm{};
     int eager = 0;             // fb_set_eager_commit: window ticks commit on the device right behind the tick
-    bool l_eager = false;      // the launched tick's eager commit is enqueued (until a rerun cancels it)
     PostRec *post = nullptr;       // post-message records {hb, free, epoch} of touched slots
     uint8_t *post_rf = nullptr, *st = nullptr;
     unsigned long long *dmask = nullptr;
@@ -207,7 +206,6 @@ struct fb_ctx {
     hipEvent_t use_ev[2] = {nullptr, nullptr};          // the tick reading device half h done
     bool stage_rec[2] = {false, false}, use_rec[2] = {false, false};
     int stage_half = 1;        // half of the last launch's copies
-    bool staged = false;       // fb_tick_stage done, fb_tick_launch_staged not yet
     int32_t st_E = 0, st_vmax = 0;
     double st_now = 0.0;
     HostPool *pool = nullptr;  // staging workers (FAASBAL_STAGE_THREADS, default 8; 1 = none)
@@ -257,8 +255,11 @@ struct fb_ctx {
     bool seg_owned = false;
     int oA_cap = 0;
     bool oA_owned = false;
+    // where the tick is in its life and what the committed state is owed (faasbal_life.h):
+    // written by the life_* transitions only, read through enter()
+    CtxCaps caps;
+    Life life;
     // last launch
-    bool launched = false, waited = false;
     double l_now = 0, l_tte = 0;
     int32_t l_E = 0;
     bool l_purge_only = false;  // fb_purge_launch: orphans reported, not dispatched
@@ -287,8 +288,6 @@ struct fb_ctx {
     uint32_t *ocnt = nullptr, *osegcnt = nullptr;
     uint32_t *xg_acc = nullptr, *xg_tk = nullptr, *ogrp = nullptr;  // exchanged group rows (phase 1 -> 2)
     uint32_t *xs_tk = nullptr;                        // k_xscan's ticket
-    bool stale_any = false;                           // lazy clears: entries of dead registrations may be in the log
-    bool l_enospc = false;                            // the launched tick's wait failed with FB_ENOSPC (log full)
     void *lc_mem = nullptr;                           // fb_log_compact's scratch (lc_plan's regions; made on first use)
     size_t lc_cap = 0;
     void *ps_mem = nullptr;                           // fb_pool_stats' scratch (ps_plan's regions; made on first use)
@@ -306,7 +305,6 @@ struct fb_ctx {
     // agrees), and whether that copy is known zero (then an idle tick's phase 1 needs no memset)
     int xpar = 0;
     bool xz_ok = false;
-    int phase = 0;                                    // 1: phase 1 enqueued; 2: phase 2 enqueued
     int shard_R = 0;                                  // > 0: round rows a relaunch asked for (FB_ERERUN)
     // contexts without deferred clears (sharded, deque, one GPU past kLdsBitmapSlots): results
     // clear their log entries in place at launch; the entries a launch cleared (per message,
@@ -316,8 +314,6 @@ struct fb_ctx {
     int64_t *undo_idx = nullptr;
     unsigned long long *undo_key = nullptr;
     uint32_t undo_tag = 0;                            // the last host launch's tag (never 0)
-    int undo_E = 0;                                   // > 0: messages of a launch not committed yet
-    bool l_failed = false;                            // the launched tick's fb_tick_wait failed: it never commits
     hipStream_t own_s = nullptr;                      // the context's own stream (fb_set_stream may borrow another)
 };
 
@@ -606,19 +602,10 @@ int win_alloc(fb_ctx *c) {
     return FB_OK;
 }
 
-// A launched window tick moves the committed window (its commit may already have run on
-// the device, eager) while the host's view of it changes only at fb_tick_commit: state
-// reads wait for that commit.
-int win_uncommitted(fb_ctx *c, const char *what) {
-    if (c->launched && c->l_win)
-        return fail(c, FB_ESTATE, "%s between the launch and the commit of a window tick: fb_tick_commit first", what);
-    return FB_OK;
-}
-
 // The deferred commit of the last tick as its own launch (when no k_ev_link takes it).
 int flush_commit(fb_ctx *c) {
-    if (!c->cm_pending) return FB_OK;
-    c->cm_pending = false;
+    if (!c->life.cm_pending) return FB_OK;
+    life_commit_ran(c->life);
     HIPCHK(c, hipSetDevice(c->device));
     Timer t(c, "commit");
     launch_commit(c->cm, t.st());
@@ -631,12 +618,12 @@ int flush_commit(fb_ctx *c) {
 // not older than s's registration (epoch), which every kernel that reads the log tests once
 // such entries may exist (live_chk).  (configs[3]: the fold's ~380 K scattered clears cost
 // 2.9 µs of the committed tick; configs[2]'s 24.6 K, ~0.5 µs.)
-bool lazy_ctx(const fb_ctx *c) { return c->paths.lazy_on && !c->shard && !c->deque; }
+bool lazy_ctx(const fb_ctx *c) { return c->paths.lazy_on && c->caps.lists; }
 
 // Before a state read hands out the log: the deferred clears, all at once (k_log_normalize),
 // after the last commit.
 int log_settle(fb_ctx *c) {
-    if (!c->stale_any) return FB_OK;
+    if (!life_settle_due(c->life)) return FB_OK;
     if (int rc_ = flush_commit(c)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->head > 0) {  // (an empty log launches nothing: no events to time)
@@ -645,33 +632,34 @@ int log_settle(fb_ctx *c) {
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
-    c->stale_any = false;
+    life_settled(c->life);
     return FB_OK;
 }
 
 // The in-place clears of a launch that was never committed, taken back: the log entries its
-// results completed are in flight again.  (Before the next launch, and before anything reads
-// or replaces the committed log once the launch's wait has failed -- log_undo_failed; between
-// a successful wait and the commit the clears stay: the commit relies on them.)
+// results completed are in flight again.  (life_gate says when: before the next launch, and
+// before anything reads the committed log once the launch's wait has failed; between a
+// successful wait and the commit the clears stay: the commit relies on them.)
 int log_undo(fb_ctx *c) {
-    if (c->undo_E <= 0) return FB_OK;
     HIPCHK(c, hipSetDevice(c->device));
     {
         Timer t(c, "log_undo");
-        launch_log_undo(c->log_slot, c->undo_idx, c->undo_key, c->undo_tag, c->undo_E, t.st());
+        launch_log_undo(c->log_slot, c->undo_idx, c->undo_key, c->undo_tag, c->life.undo_E, t.st());
     }
     HIPCHK(c, hipGetLastError());
-    c->undo_E = 0;
+    life_undone(c->life);
     return FB_OK;
 }
 
-// sync: the caller hands the log to a reader outside the context's stream
-int log_undo_failed(fb_ctx *c, bool sync = false) {
-    // (a launch still waiting to be waited for or committed keeps its clears; every failed
-    // wait sets l_failed, whether or not it also cleared `launched`)
-    if (c->undo_E <= 0 || !c->l_failed) return FB_OK;
-    if (int rc_ = log_undo(c)) return rc_;
-    if (sync) HIPCHK(c, stream_wait(c));
+// The top of every entry point: life_gate's refusal, or the duties it names, in order.
+int enter(fb_ctx *c, Call call) {
+    const Gate g = life_gate(c->life, c->caps, call);
+    if (g.duties & kFlush)
+        if (int rc_ = flush_commit(c)) return rc_;
+    if (g.refuse) return fail(c, FB_ESTATE, "%s", g.refuse);
+    if (g.duties & kUndo)
+        if (int rc_ = log_undo(c)) return rc_;
+    if (g.duties & kUndoSync) HIPCHK(c, stream_wait(c));
     return FB_OK;
 }
 
@@ -681,7 +669,7 @@ bool win_plan(fb_ctx *c) {
     WindowIn w{};
     w.win_cap = c->win_cap;
     w.mode = c->win;
-    w.lists = c->ev_head != nullptr;
+    w.lists = c->caps.lists;
     w.ev_ll = c->paths.ev_ll != 0;
     w.compact = c->compact != 0;
     w.purge_only = c->l_purge_only;
@@ -704,11 +692,11 @@ bool win_plan(fb_ctx *c) {
 PlanIn plan_input(const fb_ctx *c) {
     PlanIn in;
     in.shard = c->shard;
-    in.phase = c->phase;
+    in.phase = life_phase(c->life);
     in.world = c->world;
     in.deque = c->deque;
-    in.heartbeat = c->bud != nullptr;
-    in.lists = c->ev_head != nullptr;
+    in.heartbeat = c->caps.clears == Clears::deferred;
+    in.lists = c->caps.lists;
     in.qaos = c->qaos;
     in.compact = c->compact;
     in.cout = c->cout_slot != nullptr;
@@ -726,13 +714,13 @@ PlanIn plan_input(const fb_ctx *c) {
     in.ncu = c->ncu;
     in.max_lds = c->max_lds;
     in.win_occ = c->win_occ;
-    in.l_win = c->l_win;
+    in.l_win = c->life.win;
     in.l_nchW = c->l_nchW;
     in.pos_ok = c->pos_ok;
     in.l_resort = c->l_resort;
     in.l_purge_only = c->l_purge_only;
-    in.stale_any = c->stale_any;
-    in.cm_pending = c->cm_pending;
+    in.stale_any = c->life.stale;
+    in.cm_pending = c->life.cm_pending;
     in.cm_E = c->cm.E;
     in.cm_win = c->cm.win;
     in.cm_n_clr = c->cm.n_clr;
@@ -755,7 +743,7 @@ struct EvLists {
 // this launch's).
 EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const EvLists &l) {
     const int cur = c->cur, nxt = 1 - cur;
-    const bool defer = c->bud != nullptr;  // one-GPU heartbeat context
+    const bool defer = c->caps.clears == Clears::deferred;  // one-GPU heartbeat context
     EvArgs ea{};
     ea.E = a.E;
     ea.W = a.W;
@@ -805,7 +793,7 @@ EvArgs fill_ev_args(const fb_ctx *c, const TickPlan &p, const TickArgs &a, const
         ea.svals = c->vals[(p.passes - 1) & 1];
         return ea;
     }
-    ea.tbits_words = c->tbits ? (int)cdiv(a.W, 32) : 0;
+    ea.tbits_words = c->caps.lists ? (int)cdiv(a.W, 32) : 0;
     ea.ev_slot = c->ev_slot;
     ea.ev_head = c->ev_head;
     ea.ev_next = c->ev_next;
@@ -866,7 +854,7 @@ void fill_tick_args(const fb_ctx *c, const TickPlan &p, const EvLists &l, TickAr
     a.xw_out = c->xw[nxt];
     a.kl_out = c->kl[nxt];
     a.qrank_out = c->qrank[nxt];
-    if (c->bud) {  // one-GPU heartbeat context
+    if (c->caps.clears == Clears::deferred) {  // one-GPU heartbeat context
         a.bud = c->bud;
         a.bud_next = c->bud_next;
         a.post_infl = c->post_infl;
@@ -942,7 +930,7 @@ void fill_tick_args(const fb_ctx *c, const TickPlan &p, const EvLists &l, TickAr
         const size_t xrw = (size_t)c->world * kXRecWords;
         a.xrec = (unsigned long long *)(c->xbuf + p.xl.rec) + (size_t)c->xpar * xrw;
         a.xrows = p.xrb ? c->xbuf + p.xl.rows : nullptr;
-        if (c->l_full && c->phase == 2) a.assign_all = c->assign_all;
+        if (c->l_full && life_phase(c->life) == 2) a.assign_all = c->assign_all;
         if (a.xplan) {
             // k_xscan's outputs in the plan tables (unused on this path): per-block prefixes in
             // qpre's words, the chunk prefixes and totals in opre's
@@ -955,7 +943,7 @@ void fill_tick_args(const fb_ctx *c, const TickPlan &p, const EvLists &l, TickAr
         a.xg_acc = c->xg_acc;
         a.xg_tk = c->xg_tk;
         a.ogrp = c->ogrp;
-        if ((p.xrb || a.xplan) && c->phase == 2) {
+        if ((p.xrb || a.xplan) && life_phase(c->life) == 2) {
             a.xz = (unsigned long long *)(c->xbuf + p.xl.rec) + (size_t)(c->xpar ^ 1) * xrw;
             a.xz_words = (int)xrw;
         }
@@ -1030,7 +1018,7 @@ int launch_common_stage(fb_ctx *c, const TickPlan &p, const TickArgs &a, const E
             r.zero0 = ea.front_list;
             r.zero1 = ea.back_list;
             r.zbits = c->tbits;
-            r.zwords = c->tbits ? (int)cdiv(ea.W, 32) : 0;
+            r.zwords = c->caps.lists ? (int)cdiv(ea.W, 32) : 0;
         }
         launch_rs_pass(r, t.first(), t.last());
         ++ps;
@@ -1157,7 +1145,7 @@ int enqueue_tick(fb_ctx *c) {
         l.back = (int32_t *)(c->xbuf + p.xl.back);
         l.evs = c->xbuf + p.xl.evs;
         // (an idle tick whose records the last phase 2 zeroed has nothing else to clear)
-        if (c->phase != 2 && !(a.E == 0 && c->xz_ok)) HIPCHK(c, hipMemsetAsync(c->xbuf, 0, p.xl.c8, c->stream));
+        if (life_phase(c->life) != 2 && !(a.E == 0 && c->xz_ok)) HIPCHK(c, hipMemsetAsync(c->xbuf, 0, p.xl.c8, c->stream));
     }
     if (a.grp_on) {
         c->gpar ^= 1;
@@ -1178,7 +1166,7 @@ int enqueue_tick(fb_ctx *c) {
     c->l_cout = p.l_cout;
     if (c->shard) {
         c->l_full = c->full_assign != 0;
-        if (c->l_full && c->phase == 2) {
+        if (c->l_full && life_phase(c->life) == 2) {
             // the whole tick's assignments: at most its pending tasks plus every in-flight entry
             const int64_t need = std::max<int64_t>(1, c->l_T + c->l_head);
             if (need > c->assign_cap) {
@@ -1212,7 +1200,7 @@ int enqueue_tick(fb_ctx *c) {
     fill_tick_args(c, p, l, a);
     const EvArgs ea = p.grouping == Grouping::none ? EvArgs{} : fill_ev_args(c, p, a, l);
     // the last tick's commit, when this tick's first kernel runs it
-    if (p.commit == CommitPlan::in_ev_link || p.commit == CommitPlan::in_scan) c->cm_pending = false;
+    if (p.commit == CommitPlan::in_ev_link || p.commit == CommitPlan::in_scan) life_commit_ran(c->life);
     switch (p.kind) {
     case TickKind::window: return launch_window_tick(c, p, a, ea);
     case TickKind::shard_phase1: return launch_shard_phase1(c, p, a, ea);
@@ -1259,10 +1247,18 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
     const size_t W = (size_t)max_workers, E = (size_t)c->E_cap, F = (size_t)max_log;
     const size_t Wq = (size_t)c->Wq_cap;  // queue entries are global slots
     const size_t Qlog = Wq + 2 * E;
+    // the context kind (faasbal_life.h): message lists on one-GPU heartbeat contexts; in-flight
+    // counts and deferred clears only where the fused tick can use them (the died bitmap of the
+    // log workgroups fits in LDS), larger tables keep k_logscan and in-place clears
+    c->caps.sharded = shard != 0;
+    c->caps.deque = c->deque != 0;
+    c->caps.lists = !shard && !c->deque;
+    c->caps.clears = c->caps.lists && W <= (size_t)kLdsBitmapSlots ? Clears::deferred : Clears::in_place;
+    const bool deferred = c->caps.clears == Clears::deferred;
     // window-capable contexts (one GPU, heartbeat loop): each queue buffer holds a window
     // that slides right by the served prefix and grows at its tail (<= 2 E + tasks per tick)
     // (large tables; fb_set_window allocates them later for others)
-    c->win_cap = !shard && !c->deque && W > (size_t)kLdsBitmapSlots;
+    c->win_cap = c->caps.lists && !deferred;
     c->qcap = c->win_cap ? (int64_t)(2 * Wq + 2 * E + 4096) : (int64_t)Wq;
     const size_t Wqb = (size_t)c->qcap;
     ArenaPlan ap;
@@ -1287,7 +1283,7 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
     ap.add(&c->hb, W);
     ap.add(&c->epoch, W);
     ap.add(&c->touched, W);
-    if (!shard && !c->deque) {
+    if (c->caps.lists) {
         ap.add(&c->tbitsb[0], (W + 31) / 32);
         ap.add(&c->tbitsb[1], (W + 31) / 32);
     }
@@ -1315,7 +1311,7 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
                                         (size_t)2048 * (size_t)(std::min<int64_t>((int64_t)cdiv(E, kRsTile), kRsWideMaxBlocks) + 1)));
     ap.add(&c->front_list, E);
     ap.add(&c->back_list, E);
-    if (!shard && !c->deque) {
+    if (c->caps.lists) {
         ap.add(&c->ev_head, W);
         ap.add(&c->ev_next, E);
     }
@@ -1361,9 +1357,7 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
         ap.add(&c->post_nf, W);
         ap.add(&c->c_tok, Qlog);
     }
-    // in-flight counts only where the fused tick can use them (the died bitmap of the
-    // log workgroups fits in LDS); larger tables keep k_logscan and in-place clears
-    if (!shard && !c->deque && W <= (size_t)kLdsBitmapSlots) {
+    if (deferred) {
         ap.add(&c->bud, W);
         ap.add(&c->bud_next, W);
         ap.add(&c->post_infl, W);
@@ -1372,7 +1366,7 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
         ap.add(&c->orph_dense, F);
     }
     // window ticks leave their orphans in per-tile segments too (gathered when read)
-    if (c->win_cap && !(!shard && !c->deque && W <= (size_t)kLdsBitmapSlots)) ap.add(&c->orph_dense, F);
+    if (c->win_cap) ap.add(&c->orph_dense, F);
     if (shard) {
         ap.add(&c->lseq, F);
         ap.add(&c->ocnt, tab);
@@ -1388,7 +1382,7 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
         ap.add(&c->ogrp, ng * kXGroupR);
     }
     // every context that clears in place (no bud / ctag above) notes its clears (k_log_undo)
-    if (shard || c->deque || W > (size_t)kLdsBitmapSlots) {
+    if (!deferred) {
         ap.add(&c->undo_idx, E);
         ap.add(&c->undo_key, E);
     }
@@ -1429,12 +1423,12 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
     }
     if (!rc && hipMemset(c->touched, 0, W * 4) != hipSuccess) rc = FB_EHIP;
     for (int p = 0; p < 2 && !rc; ++p)
-        if (c->tbitsb[p] && hipMemset(c->tbitsb[p], 0, (W + 31) / 32 * 4) != hipSuccess) rc = FB_EHIP;
+        if (c->caps.lists && hipMemset(c->tbitsb[p], 0, (W + 31) / 32 * 4) != hipSuccess) rc = FB_EHIP;
     if (!rc) c->tbits = c->tbitsb[c->tick & 1];
     for (int p = 0; p < 2 && !rc; ++p)
         if (hipMemset(c->grp[p], 0, kGrpWords * 4) != hipSuccess) rc = FB_EHIP;
     if (!rc && hipMemset(c->reg, 0, W) != hipSuccess) rc = FB_EHIP;
-    if (!rc && c->ev_head && hipMemset(c->ev_head, 0, W * 8) != hipSuccess) rc = FB_EHIP;  // stamp 0: never a launch's
+    if (!rc && c->caps.lists && hipMemset(c->ev_head, 0, W * 8) != hipSuccess) rc = FB_EHIP;  // stamp 0: never a launch's
     if (rc) {
         fb_destroy(c);
         return rc;
@@ -1512,9 +1506,7 @@ int fb_load_state(fb_ctx *c, int32_t n_workers, const uint8_t *registered, const
                   const double *last_heartbeat, const uint32_t *epoch, const int32_t *queue, int64_t queue_len,
                   const int32_t *log_slot, int64_t log_len) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
-    c->stale_any = false;  // a loaded log holds only live entries
-    if (c->shard) return fail(c, FB_ESTATE, "sharded context: use fb_load_shard");
+    if (int rc_ = enter(c, Call::load_state)) return rc_;
     if (n_workers < 0 || n_workers > c->W_cap) return fail(c, FB_EINVAL, "n_workers %d outside [0, %d]", n_workers, c->W_cap);
     if (log_len < 0 || log_len > c->log_cap) return fail(c, FB_EINVAL, "log_len %lld exceeds capacity", (long long)log_len);
     if (queue_len < 0 || queue_len > (c->deque ? c->Wq_cap : n_workers))
@@ -1592,14 +1584,14 @@ int fb_load_state(fb_ctx *c, int32_t n_workers, const uint8_t *registered, const
             for (int64_t i = 0; i < log_len; ++i)
                 if (lg[i] >= 0 && (!reg[lg[i]] || (uint64_t)i < (uint64_t)epv[lg[i]])) lg[i] = -1;
         HIPCHK(c, hipMemcpy(c->log_slot, lg.data(), (size_t)log_len * 4, hipMemcpyHostToDevice));
-        if (c->bud) {
+        if (c->caps.clears == Clears::deferred) {
             std::vector<int32_t> bud(W ? W : 1, 0);
             for (int64_t i = 0; i < log_len; ++i)
                 if (lg[i] >= 0) ++bud[lg[i]];
             for (size_t s = 0; s < W; ++s) bud[s] = reg[s] ? (int32_t)((uint32_t)bud[s] + (uint32_t)free_processes[s]) : 0;
             if (W) HIPCHK(c, hipMemcpy(c->bud, bud.data(), W * 4, hipMemcpyHostToDevice));
         }
-    } else if (c->bud && W) {
+    } else if (c->caps.clears == Clears::deferred && W) {
         std::vector<int32_t> bud(W);
         for (size_t s = 0; s < W; ++s) bud[s] = reg[s] ? free_processes[s] : 0;
         HIPCHK(c, hipMemcpy(c->bud, bud.data(), W * 4, hipMemcpyHostToDevice));
@@ -1612,17 +1604,14 @@ int fb_load_state(fb_ctx *c, int32_t n_workers, const uint8_t *registered, const
     c->maxc_hint = maxc;
     c->last_L = -1;
     c->last_O = 0;
-    c->launched = c->waited = false;
-    c->undo_E = 0;  // an abandoned launch's notes name entries of the log this one replaced
+    life_replaced(c->life);
     return FB_OK;
 }
 
 int fb_read_state(fb_ctx *c, uint8_t *registered, int32_t *free_processes, double *last_heartbeat, uint32_t *epoch,
                   int32_t *queue, int64_t *queue_len, int32_t *log_slot, int64_t *log_len) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = win_uncommitted(c, "fb_read_state")) return rc_;
-    if (int rc_ = flush_commit(c)) return rc_;
-    if (int rc_ = log_undo_failed(c)) return rc_;  // a failed launch's in-place clears
+    if (int rc_ = enter(c, Call::read_state)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, stream_wait(c));
     const size_t W = (size_t)c->W;
@@ -1661,9 +1650,7 @@ int fb_load_shard(fb_ctx *c, int32_t slot_base, int32_t n_workers, const uint8_t
                   const int32_t *queue, int64_t queue_len, const int32_t *log_slot, const uint32_t *log_seq,
                   int64_t log_len, int64_t log_head) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
-    c->stale_any = false;  // a loaded log holds only live entries
-    if (!c->shard) return fail(c, FB_ESTATE, "fb_load_shard on a one-GPU context");
+    if (int rc_ = enter(c, Call::load_shard)) return rc_;
     if (n_workers < 0 || n_workers > c->W_cap || slot_base < 0 || (int64_t)slot_base + n_workers > c->W_global)
         return fail(c, FB_EINVAL, "slot range [%d, %d + %d) outside the %d-slot table", slot_base, slot_base, n_workers,
                     c->W_global);
@@ -1743,17 +1730,13 @@ int fb_load_shard(fb_ctx *c, int32_t slot_base, int32_t n_workers, const uint8_t
     // (maxc above) would differ between ranks.  A fill level beyond it relaunches wider.
     (void)maxc;
     c->maxc_hint = 1;
-    c->launched = c->waited = false;
-    c->phase = 0;
-    c->undo_E = 0;  // an abandoned launch's notes name entries of the log this one replaced
+    life_replaced(c->life);
     return FB_OK;
 }
 
 int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {
     if (!c || !inflight) return FB_EINVAL;
-    if (int rc_ = win_uncommitted(c, "fb_read_inflight")) return rc_;
-    if (int rc_ = flush_commit(c)) return rc_;
-    if (!c->bud) return fail(c, FB_ESTATE, "in-flight counts exist on one-GPU heartbeat contexts only");
+    if (int rc_ = enter(c, Call::read_inflight)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, stream_wait(c));
     const size_t W = (size_t)c->W;
@@ -1772,19 +1755,9 @@ int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {
 // (k_lc_flag, k_lc_scan write only the scratch), synchronise, check, and only then move.
 int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept) {
     if (!c) return FB_EINVAL;
-    if (c->shard)
-        return fail(c, FB_ESTATE, "fb_log_compact on a sharded context: its sequence numbers are global across ranks");
     if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
-    if (c->staged) return fail(c, FB_ESTATE, "fb_log_compact with staged events pending: their sequences would go stale");
-    if (c->launched && c->waited)
-        return fail(c, FB_ESTATE, "fb_log_compact between a tick's wait and its commit: fb_tick_commit first");
-    // (a tick whose wait failed with FB_ENOSPC read only committed state: it is discarded below,
-    // as fb_load_state discards it; a window tick's launch moved the window, which this cannot undo)
-    if (c->launched && (!c->l_enospc || c->l_win))
-        return fail(c, FB_ESTATE, "fb_log_compact with a tick launched: fb_tick_wait and fb_tick_commit first");
-    if (int rc_ = flush_commit(c)) return rc_;
-    // the discarded tick's results completed nothing: its clears are taken back before the count
-    if (int rc_ = log_undo_failed(c)) return rc_;
+    // (a discarded tick's results completed nothing: its clears are taken back before the count)
+    if (int rc_ = enter(c, Call::log_compact)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     const LcPlan p = lc_plan(c->head, c->W, kept_seq != nullptr);
     if (p.bytes > c->lc_cap) {
@@ -1806,7 +1779,7 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     a.head = c->head;
     a.W = c->W;
     a.nt = p.nt;
-    a.live_chk = c->stale_any ? 1 : 0;
+    a.live_chk = c->life.stale ? 1 : 0;
     a.reg = c->reg;
     a.epoch = c->epoch;
     a.bitmap = (unsigned long long *)(base + p.bitmap);
@@ -1845,10 +1818,7 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     HIPCHK(c, stream_wait(c));
     if (kept_seq && live) HIPCHK(c, hipMemcpy(kept_seq, a.kept, (size_t)live * 8, hipMemcpyDeviceToHost));
     c->head = (int64_t)live;
-    c->stale_any = false;  // a compacted log holds only live entries
-    c->launched = c->waited = false;  // (the discarded FB_ENOSPC tick)
-    c->undo_E = 0;  // (notes name the old numbering)
-    c->l_enospc = false;
+    life_replaced(c->life);  // (with it the discarded FB_ENOSPC tick)
     if (n_kept) *n_kept = (int64_t)live;
     return FB_OK;
 }
@@ -1871,15 +1841,7 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
         if (!std::isfinite(now) || !std::isfinite(tte))
             return fail(c, FB_EINVAL, "now %g / tte %g must be finite", now, tte);
     }
-    if (c->shard)
-        return fail(c, FB_ESTATE, "fb_pool_stats on a sharded context: the pool is the group's, a summary needs a collective");
-    if (c->staged) return fail(c, FB_ESTATE, "fb_pool_stats with staged events pending: launch and commit their tick first");
-    if (c->launched && c->waited)
-        return fail(c, FB_ESTATE, "fb_pool_stats between a tick's wait and its commit: fb_tick_commit first");
-    if (c->launched)
-        return fail(c, FB_ESTATE, "fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first");
-    if (int rc_ = flush_commit(c)) return rc_;  // (observably an immediate commit)
-    if (int rc_ = log_undo_failed(c)) return rc_;  // a failed launch's in-place clears
+    if (int rc_ = enter(c, Call::pool_stats)) return rc_;  // (its flush: observably an immediate commit)
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->ps_out) {
         if (hipHostMalloc((void **)&c->ps_out, kPsCols * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
@@ -1913,7 +1875,7 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     a.nt = p.nt;
     a.hb_chk = hbc ? 1 : 0;
     a.tomb_chk = c->win_cap ? 1 : 0;
-    a.live_chk = c->stale_any ? 1 : 0;
+    a.live_chk = c->life.stale ? 1 : 0;
     a.Qn = c->Qn;
     a.qoff = c->qoff;
     a.head = c->head;
@@ -1978,7 +1940,7 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     s.log_head = c->head;
     s.inflight = r[kPsLive];
     s.inflight_expired = r[kPsLiveExp];
-    s.inflight_max = c->bud ? r[kPsInflMax] : -1;
+    s.inflight_max = c->caps.clears == Clears::deferred ? r[kPsInflMax] : -1;
     const bool any_hb = hbc && r[kPsHbN] > 0;
     memcpy(&s.oldest_hb, &r[kPsHbMin], 8);
     memcpy(&s.newest_hb, &r[kPsHbMax], 8);
@@ -1991,8 +1953,7 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
 
 int fb_read_shard_log(fb_ctx *c, uint32_t *log_seq, int64_t *log_len, int64_t *log_head) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
-    if (!c->shard) return fail(c, FB_ESTATE, "fb_read_shard_log on a one-GPU context");
+    if (int rc_ = enter(c, Call::read_shard_log)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, stream_wait(c));
     if (log_seq && c->head_local)
@@ -2016,8 +1977,10 @@ int fb_bind_exchange(fb_ctx *c, void *device_buffer, int64_t bytes) {
 
 int fb_exchange_bytes(fb_ctx *c, int32_t n_events, int64_t *bytes) {
     if (!c || !bytes) return FB_EINVAL;
+    if (int rc_ = enter(c, Call::exchange_bytes)) return rc_;
+    const bool launched = life_launched(c->life);
     const int64_t E = n_events < 0 ? c->E_cap : n_events;
-    const int64_t Qn = n_events < 0 ? c->Wq_cap : (c->launched ? c->l_Qn : c->Qn);
+    const int64_t Qn = n_events < 0 ? c->Wq_cap : (launched ? c->l_Qn : c->Qn);
     // the maximum: room for the wide form or for the block rows of a <= kRFused-row table,
     // whichever is larger; a launched tick: its own width and rows
     const int64_t Qlog = Qn + 2 * E;
@@ -2032,7 +1995,7 @@ int fb_exchange_bytes(fb_ctx *c, int32_t n_events, int64_t *bytes) {
                                     xlayout(c->world, E, Qlog, 1, xrows_bytes(c->world, kXGroupR, Qlog),
                                             xgrows_bytes(c->world, kXGroupR, Qlog)).total});
     } else {
-        const int R = c->launched ? c->l_R : kRFused;
+        const int R = launched ? c->l_R : kRFused;
         const XRows xr = exchange_rows(c->paths, c->world, R, Qlog);
         *bytes = (int64_t)xlayout(c->world, E, Qlog, xc_width(R), xr.rows, xr.grows).total;
     }
@@ -2049,10 +2012,9 @@ int fb_set_stream(fb_ctx *c, void *stream) {
 
 int fb_tick_continue(fb_ctx *c) {
     if (!c) return FB_EINVAL;
-    if (!c->shard) return fail(c, FB_ESTATE, "fb_tick_continue on a one-GPU context");
-    if (!c->launched || c->phase != 1) return fail(c, FB_ESTATE, "fb_tick_continue without fb_tick_launch");
+    if (int rc_ = enter(c, Call::tick_continue)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
-    c->phase = 2;
+    life_continue(c->life);
     return enqueue_tick(c);
 }
 
@@ -2084,6 +2046,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
     if (n_events < 0 || n_events > c->E_cap) return fail(c, FB_EINVAL, "n_events %d outside [0, %d]", n_events, c->E_cap);
     if (n_events && (!kind || !slot || !val || !ts))
         return fail(c, FB_EINVAL, "event arrays must be non-NULL");
+    if (int rc_ = enter(c, Call::stage)) return rc_;
     const int E = n_events;
     const int half = c->stage_half ^ 1;
     // One pass over the caller's arrays: validate (branch-free; the per-event loop
@@ -2122,7 +2085,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         // a batch already in this GPU's memory (e.g. parsed there, or staged ahead): the
         // tick reads it in place and its first kernel checks it (an invalid message is
         // overwritten with a harmless one and fb_tick_wait names it); no host pass
-        if (!(c->ev_head && c->paths.ev_ll))
+        if (!(c->caps.lists && c->paths.ev_ll))
             return fail(c, FB_EINVAL, "device-resident messages need a one-GPU heartbeat context");
         c->st_dev[0] = kind;
         c->st_dev[1] = slot;
@@ -2131,7 +2094,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         c->st_dev[4] = seq;
         c->st_res = true;
         c->st_chk[0] = c->st_chk[1] = c->st_chk[2] = kind;  // device-checked (names come from bad_min)
-        c->staged = true;
+        life_stage(c->life, true);
         c->st_E = E;
         c->st_vmax = 0;
         c->st_now = now;
@@ -2164,7 +2127,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         // (slots, kinds, timestamps; fb_tick_wait names the first offending event and the
         // tick commits nothing): the host does not read them at all.  The round table is
         // then sized from the last tick's free counts (a wider one is a rerun away).
-        const bool dev_chk = direct && c->ev_head && c->paths.ev_ll;
+        const bool dev_chk = direct && c->caps.lists && c->paths.ev_ll;
         auto part = [&](int pi) {
             if (dev_chk) {
                 pbad[pi] = 0;
@@ -2202,7 +2165,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
             vmax = std::max(vmax, pvmax[pi]);
         }
         for (int i = 0; bad && i < E; ++i) {
-            c->staged = false;
+            life_stage(c->life, false);
             c->stage_rec[half] = false;  // nothing was copied out of this half
             if ((uint32_t)slot[i] >= Wv) return fail(c, FB_EINVAL, "event %d: slot %d outside [0, %u)", i, slot[i], Wv);
             if (kind[i] > FB_EV_OTHER) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, kind[i]);
@@ -2222,7 +2185,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         char *h = (char *)c->h_stage + (size_t)half * ecap * 32;
         if (int rc = stage_copies(c, half, h, h + ecap, h + ecap * 5, h + ecap * 9, h + ecap * 17, E)) return rc;
     }
-    c->staged = true;
+    life_stage(c->life, true);
     c->st_E = E;
     c->st_vmax = vmax;
     c->st_now = now;
@@ -2233,10 +2196,8 @@ static CommitArgs commit_args(fb_ctx *c, bool eager);
 
 int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     if (!c) return FB_EINVAL;
-    if (!c->staged) return fail(c, FB_ESTATE, "fb_tick_launch_staged without fb_tick_stage");
-    if (c->launched && c->l_eager)
-        return fail(c, FB_ESTATE, "the last tick was committed eagerly: fb_tick_wait and fb_tick_commit first");
     if (n_pending < 0) return fail(c, FB_EINVAL, "n_pending < 0");
+    if (int rc_ = enter(c, Call::launch)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     const int E = c->st_E;
     const int half = c->stage_half ^ 1;
@@ -2260,7 +2221,6 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
         c->ev_seq = c->evq[half];
     }
     c->stage_half = half;
-    c->staged = false;
     const double now = c->st_now;
     c->l_now = now;
     c->l_tte = c->deque ? __builtin_inf() : tte;  // start() has no liveness: nobody ever expires
@@ -2270,9 +2230,8 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     c->l_head_local = c->head_local;
     c->l_Qn = c->Qn;
     c->l_qoff = c->qoff;
-    c->phase = 1;
     c->tick += 1;  // per-launch stamp: a relaunch with other messages never sees this launch's marks
-    if (c->tbitsb[0]) c->tbits = c->tbitsb[c->tick & 1];  // the last tick's bits stay for its deferred commit
+    if (c->caps.lists) c->tbits = c->tbitsb[c->tick & 1];  // the last tick's bits stay for its deferred commit
     c->l_R = choose_R(std::max(c->maxc_hint, c->st_vmax));
     // sharded: the round table starts at <= 128 rows (one byte per exchanged c: every
     // round below the table is exact, 255 > 128); a fill level reaching the table makes
@@ -2280,12 +2239,9 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     if (c->shard) c->l_R = std::min(c->shard_R > 0 ? c->shard_R : std::min(c->l_R, kRFused), kShardMaxR);
     c->reruns = 0;
     c->l_resort = false;
-    c->launched = true;
-    c->waited = false;
-    c->l_enospc = false;
     c->l_purge_only = c->next_purge_only;
     c->next_purge_only = false;
-    c->l_win = win_plan(c);
+    life_launch(c->life, c->caps, E, win_plan(c));
     for (int j = 0; j < 3; ++j) c->l_chk[j] = E ? c->st_chk[j] : nullptr;
     c->hout->bad_ev = 0;  // set by k_ev_link when it finds an invalid message
     // lengths every finished tick writes: a value left unwritten reads back as -1 and fails
@@ -2293,19 +2249,12 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
     c->hout->new_qlen = -1;
     c->hout->win_head = -1;
     c->hout->win_qlen = -1;
-    // the last launch was never committed (abandoned, failed, or asked for this relaunch)
-    if (int rc_ = log_undo(c)) return rc_;
-    c->l_failed = false;
-    if (c->undo_idx) {
-        // one tag per host launch: the notes of fb_tick_wait's reruns and of a sharded
-        // tick's phase 2 belong to this launch too (notes under older tags are never applied)
-        if (++c->undo_tag == 0) c->undo_tag = 1;
-        c->undo_E = E;
-    }
+    // one tag per host launch: the notes of fb_tick_wait's reruns and of a sharded
+    // tick's phase 2 belong to this launch too (notes under older tags are never applied)
+    if (c->caps.clears == Clears::in_place && ++c->undo_tag == 0) c->undo_tag = 1;
     const int rc = enqueue_tick(c);
     if (rc) return rc;
-    c->l_eager = false;
-    if (c->eager && c->l_win) {
+    if (c->eager && c->life.win) {
         // eager: the window tick's commit right behind it on the stream; it commits only
         // if the tick finished as a window tick (fb_tick_wait reruns it otherwise)
         const CommitArgs a = commit_args(c, true);
@@ -2313,7 +2262,7 @@ int fb_tick_launch_staged(fb_ctx *c, double tte, int64_t n_pending) {
         Timer t(c, "commit");
         launch_commit(a, t.st());
         HIPCHK(c, hipGetLastError());
-        c->l_eager = true;
+        life_eager_enqueued(c->life);
     }
     if (E && !c->l_res) {  // (a device-resident batch used no half)
         // the next copy into this device half waits for the tick's reads (a rerun in
@@ -2363,7 +2312,7 @@ static int check_lengths(fb_ctx *c) {
     if (c->shard && (p.n_local < 0 || p.n_local > N))
         return fail(c, FB_EHIP, "device-reported local dispatches %lld outside [0, %lld]", (long long)p.n_local,
                     (long long)N);
-    if (c->l_win) {
+    if (c->life.win) {
         if (p.win_head < c->l_qoff || p.new_qlen < 0 || p.win_head > c->qcap || p.new_qlen > c->qcap - p.win_head)
             return fail(c, FB_EHIP, "device-reported window [%lld, +%lld) outside the queue buffer [%lld, %lld)",
                         (long long)p.win_head, (long long)p.new_qlen, (long long)c->l_qoff, (long long)c->qcap);
@@ -2378,112 +2327,114 @@ static int check_lengths(fb_ctx *c) {
     return FB_OK;
 }
 
-static int tick_wait(fb_ctx *c, fb_tick_result *res);
+static int tick_wait(fb_ctx *c, fb_tick_result *res, Wait &o);
 
 int fb_tick_wait(fb_ctx *c, fb_tick_result *res) {
     if (!c) return FB_EINVAL;
-    if (!c->launched) return fail(c, FB_ESTATE, "fb_tick_wait without fb_tick_launch");
-    if (c->shard && c->phase != 2) return fail(c, FB_ESTATE, "sharded tick: exchange, then fb_tick_continue");
-    const int rc = tick_wait(c, res);
-    // whatever failed, this launch never commits: a reader of the committed state takes its
-    // in-place clears back (log_undo_failed) without waiting for the next launch
-    if (rc) c->l_failed = true;
-    return rc;
+    if (int rc_ = enter(c, Call::wait)) return rc_;
+    for (;;) {
+        // the one place a wait's outcome moves the tick on.  Whatever failed, the launch never
+        // commits: a reader of the committed state takes its in-place clears back (life_gate)
+        // without waiting for the next launch
+        Wait o = Wait::other;
+        int rc = tick_wait(c, res, o);
+        life_wait_done(c->life, o);
+        if (o != Wait::rerun && o != Wait::rerun_general) return rc;
+        // the same functional tick again (a rerun cancels an eager commit: its kernel found the
+        // tick unfinished and committed nothing; the rerun's commit is the ordinary one)
+        c->reruns++;
+        if ((rc = enqueue_tick(c))) {
+            life_wait_done(c->life, Wait::other);
+            return rc;
+        }
+    }
 }
 
-static int tick_wait(fb_ctx *c, fb_tick_result *res) {
+// One round: wait for the launched tick and say what it left (o).  A rerun is set up here and
+// enqueued by the caller.
+static int tick_wait(fb_ctx *c, fb_tick_result *res, Wait &o) {
     HIPCHK(c, hipSetDevice(c->device));
-    for (bool first = true;; first = false) {
-        if (first && c->l_eager) {
-            // the tick's results are final when its last kernel is: the host goes on while
-            // the eager commit runs (the next launch queues behind it)
-            hipError_t e;
-            while ((e = hipEventQuery(c->tick_ev)) == hipErrorNotReady) {
-            }
-            HIPCHK(c, e);
-        } else {
-            HIPCHK(c, stream_wait(c));
+    if (c->life.eager) {
+        // the tick's results are final when its last kernel is: the host goes on while
+        // the eager commit runs (the next launch queues behind it)
+        hipError_t e;
+        while ((e = hipEventQuery(c->tick_ev)) == hipErrorNotReady) {
         }
-        // any rerun below cancels an eager commit (its kernel found the tick unfinished and
-        // committed nothing); the rerun's commit is the ordinary one
-        if (c->l_chk[0] && c->hout->bad_ev) {
-            c->l_eager = false;
-            // the batch was left to the device's check: name the first offending event; the
-            // tick is not committed (its launch read only committed state)
-            c->launched = false;
-            // the first offending message's index (k_ev_link atomicMins it for every checked
-            // batch): read, and reset for the next checked batch whatever its kind
-            int32_t bi = 0x7f7f7f7f;
-            const int32_t none = 0x7f7f7f7f;
-            HIPCHK(c, hipMemcpy(&bi, c->bad_min, 4, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(c->bad_min, &none, 4, hipMemcpyHostToDevice));
-            if (c->l_res) {
-                // a device-resident batch: the index from the device
-                return fail(c, FB_EINVAL, "event %d: invalid message (slot outside [0, %d), unknown kind, or a "
-                            "timestamp decreasing or past now)", bi, c->W);
-            }
-            const uint8_t *k = (const uint8_t *)c->l_chk[0];
-            const int32_t *sl = (const int32_t *)c->l_chk[1];
-            const double *ts = (const double *)c->l_chk[2];
-            for (int i = 0; i < c->l_E; ++i) {
-                if ((uint32_t)sl[i] >= (uint32_t)c->W) return fail(c, FB_EINVAL, "event %d: slot %d outside [0, %d)", i, sl[i], c->W);
-                if (k[i] > FB_EV_OTHER) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, k[i]);
-                if (!(ts[i] <= c->l_now) || (i && ts[i] < ts[i - 1]))
-                    return fail(c, FB_EINVAL, "event %d: timestamps must be non-decreasing and <= now", i);
-            }
-            return fail(c, FB_EINVAL, "invalid message in the batch");
+        HIPCHK(c, e);
+    } else {
+        HIPCHK(c, stream_wait(c));
+    }
+    if (c->l_chk[0] && c->hout->bad_ev) {
+        // the batch was left to the device's check: name the first offending event; the
+        // tick is not committed (its launch read only committed state)
+        o = Wait::invalid_message;
+        // the first offending message's index (k_ev_link atomicMins it for every checked
+        // batch): read, and reset for the next checked batch whatever its kind
+        int32_t bi = 0x7f7f7f7f;
+        const int32_t none = 0x7f7f7f7f;
+        HIPCHK(c, hipMemcpy(&bi, c->bad_min, 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->bad_min, &none, 4, hipMemcpyHostToDevice));
+        if (c->l_res) {
+            // a device-resident batch: the index from the device
+            return fail(c, FB_EINVAL, "event %d: invalid message (slot outside [0, %d), unknown kind, or a "
+                        "timestamp decreasing or past now)", bi, c->W);
         }
-        if (c->l_used_ll && c->hout->resort) {
-            c->l_eager = false;
-            // a slot got more messages than k_ev_apply_ll sorts in registers: the same
-            // functional tick again, grouped by the radix sort
-            if (c->reruns > 4) return fail(c, FB_EHIP, "event regrouping did not converge");
-            c->l_resort = true;
-            c->l_win = false;  // the sorted path purges in k_scan: a general tick
-            c->reruns++;
-            int rc = enqueue_tick(c);
-            if (rc) return rc;
-            continue;
+        const uint8_t *k = (const uint8_t *)c->l_chk[0];
+        const int32_t *sl = (const int32_t *)c->l_chk[1];
+        const double *ts = (const double *)c->l_chk[2];
+        for (int i = 0; i < c->l_E; ++i) {
+            if ((uint32_t)sl[i] >= (uint32_t)c->W) return fail(c, FB_EINVAL, "event %d: slot %d outside [0, %d)", i, sl[i], c->W);
+            if (k[i] > FB_EV_OTHER) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, k[i]);
+            if (!(ts[i] <= c->l_now) || (i && ts[i] < ts[i - 1]))
+                return fail(c, FB_EINVAL, "event %d: timestamps must be non-decreasing and <= now", i);
         }
-        if (c->l_win && (c->hout->status == 3 || c->hout->win_ovf)) {
-            c->l_eager = false;
-            // the window tick could not finish inside its window (a fill level above 0, an
-            // unserved front, a first unserved element past the scanned prefix, no room at
-            // the tail): the same functional tick on the general path
-            if (c->hout->status == 3 && (int64_t)c->l_nchW * kWinCh < c->l_Qn)  // the scanned prefix was short
-                c->win_slack = std::min<int64_t>(2 * c->win_slack, 1 << 24);
-            c->l_win = false;
-            c->win_fallbacks++;
-            c->reruns++;
-            int rc = enqueue_tick(c);
-            if (rc) return rc;
-            continue;
-        }
-        if (c->hout->status == 0) break;
-        c->l_eager = false;
-        if (c->hout->status == 2) c->l_enospc = true;
-        if (c->hout->status == 2)
-            return fail(c, FB_ENOSPC, "in-flight log full: %lld entries + this tick's dispatches exceed %lld",
-                        (long long)c->l_head, (long long)c->log_cap);
-        // the queue holds free counts beyond the round table: widen and rerun
-        if (c->shard) {
-            // the exchange runs between the phases, so the caller relaunches: the same tick
-            // with a table sized by the max free count seen (clamped to the exchange width)
-            const int R = choose_R(c->hout->maxc);
-            if (c->l_R >= kShardMaxR || R <= c->l_R)
-                return fail(c, FB_ERANGE, "sharded tick: fill level beyond a %d-round table (max free %d)", c->l_R,
-                            c->hout->maxc);
-            c->shard_R = std::min(R, kShardMaxR);
-            return fail(c, FB_ERERUN, "sharded tick: the fill level reaches the %d-round table; relaunch (%d rows)",
-                        c->l_R, c->shard_R);
-        }
+        return fail(c, FB_EINVAL, "invalid message in the batch");
+    }
+    if (c->l_used_ll && c->hout->resort) {
+        // a slot got more messages than k_ev_apply_ll sorts in registers: the same
+        // functional tick again, grouped by the radix sort
+        if (c->reruns > 4) return fail(c, FB_EHIP, "event regrouping did not converge");
+        c->l_resort = true;
+        o = Wait::rerun_general;  // the sorted path purges in k_scan: a general tick
+        return FB_OK;
+    }
+    if (c->life.win && (c->hout->status == 3 || c->hout->win_ovf)) {
+        // the window tick could not finish inside its window (a fill level above 0, an
+        // unserved front, a first unserved element past the scanned prefix, no room at
+        // the tail): the same functional tick on the general path
+        if (c->hout->status == 3 && (int64_t)c->l_nchW * kWinCh < c->l_Qn)  // the scanned prefix was short
+            c->win_slack = std::min<int64_t>(2 * c->win_slack, 1 << 24);
+        c->win_fallbacks++;
+        o = Wait::rerun_general;
+        return FB_OK;
+    }
+    if (c->hout->status == 2) {
+        o = Wait::log_full;
+        return fail(c, FB_ENOSPC, "in-flight log full: %lld entries + this tick's dispatches exceed %lld",
+                    (long long)c->l_head, (long long)c->log_cap);
+    }
+    // the queue holds free counts beyond the round table: widen and rerun
+    if (c->hout->status != 0 && c->shard) {
+        // the exchange runs between the phases, so the caller relaunches: the same tick
+        // with a table sized by the max free count seen (clamped to the exchange width)
         const int R = choose_R(c->hout->maxc);
+        o = Wait::too_narrow;
+        if (c->l_R >= kShardMaxR || R <= c->l_R)
+            return fail(c, FB_ERANGE, "sharded tick: fill level beyond a %d-round table (max free %d)", c->l_R,
+                        c->hout->maxc);
+        c->shard_R = std::min(R, kShardMaxR);
+        o = Wait::relaunch_wanted;
+        return fail(c, FB_ERERUN, "sharded tick: the fill level reaches the %d-round table; relaunch (%d rows)",
+                    c->l_R, c->shard_R);
+    }
+    if (c->hout->status != 0) {
+        const int R = choose_R(c->hout->maxc);
+        o = Wait::too_narrow;
         if (R <= c->l_R || c->reruns > 4)
             return fail(c, FB_ERANGE, "fill level beyond the round table (maxc %d, R %d)", c->hout->maxc, c->l_R);
         c->l_R = R;
-        c->reruns++;
-        int rc = enqueue_tick(c);
-        if (rc) return rc;
+        o = Wait::rerun;
+        return FB_OK;
     }
     if (c->paths.fault_qlen >= 0) {
         // (a window tick reported the injected length from the device already)
@@ -2492,8 +2443,7 @@ static int tick_wait(fb_ctx *c, fb_tick_result *res) {
         c->paths.fault_qlen = -1;
     }
     if (int rc_ = check_lengths(c)) {
-        c->l_eager = false;
-        c->launched = false;  // the tick is not committed (its launch read only committed state)
+        o = Wait::lengths_rejected;  // the tick is not committed (its launch read only committed state)
         return rc_;
     }
     const HostOut &p = *c->hout;
@@ -2503,7 +2453,7 @@ static int tick_wait(fb_ctx *c, fb_tick_result *res) {
     fb_tick_result r{};
     r.n_assigned = p.N_eff;
     r.n_orphans = p.O;
-    r.queue_len = c->l_win ? p.win_qlen : (int64_t)p.new_qlen;
+    r.queue_len = c->life.win ? p.win_qlen : (int64_t)p.new_qlen;
     r.log_head = c->l_head + p.N_eff;
     r.n_evicted = (int32_t)p.n_evicted;
     r.fill_level = p.L;
@@ -2512,7 +2462,7 @@ static int tick_wait(fb_ctx *c, fb_tick_result *res) {
     r.n_local = c->shard ? p.n_local : p.N_eff;
     r.n_orphans_local = c->shard ? p.O_local : p.O;
     c->last = r;
-    c->waited = true;
+    o = Wait::ok;
     if (res) *res = r;
     return FB_OK;
 }
@@ -2548,11 +2498,11 @@ static CommitArgs commit_args(fb_ctx *c, bool eager) {
         a.oseg_tiles = c->l_nbf;
         a.nbo = (int)cdiv(c->l_nbf, kWaves);
     }
-    a.n_clr = c->ev_clr ? c->l_E : 0;  // one-GPU heartbeat: the results' completed entries
+    a.n_clr = c->caps.clears == Clears::deferred ? c->l_E : 0;  // one-GPU heartbeat: the results' completed entries
     a.ev_clr = c->ev_clr;
     a.bud = c->bud;
     a.bud_next = c->bud_next;
-    if (c->l_win) {
+    if (c->life.win) {
         // the window moves: positions of slots that left become tombstones, kept slots that
         // got messages take their post-message counts, appended slots their positions
         a.win = 1;
@@ -2580,37 +2530,34 @@ static CommitArgs commit_args(fb_ctx *c, bool eager) {
 
 int fb_tick_commit(fb_ctx *c) {
     if (!c) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "fb_tick_commit without a waited tick");
+    if (int rc_ = enter(c, Call::commit)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n_orph = c->last.n_orphans_local;
-    if (c->l_eager) {
+    bool deferred = false;
+    if (c->life.eager) {
         // the device committed the tick right behind it (fb_tick_launch_staged)
-    } else if (c->W > 0 || n_orph > 0 || (c->ev_clr && c->l_E > 0)) {
-        const bool defer = c->ev_head && c->paths.ev_ll && !c->l_win;
+    } else if (c->W > 0 || n_orph > 0 || (c->caps.clears == Clears::deferred && c->l_E > 0)) {
         const CommitArgs a = commit_args(c, false);
-        if (defer) {  // (by default a window tick's commit runs at once)
+        deferred = c->caps.lists && c->paths.ev_ll && !c->life.win;
+        if (deferred) {  // (by default a window tick's commit runs at once)
             // deferred: the next launch's k_ev_link runs it (or flush_commit)
             c->cm = a;
-            c->cm_pending = true;
         } else {
             Timer t(c, "commit");
             launch_commit(a, t.st());
             HIPCHK(c, hipGetLastError());
         }
     }
-    c->l_eager = false;
-    if (lazy_ctx(c) && c->last.n_orphans > 0) c->stale_any = true;  // its orphans stay in the log
     c->cur = 1 - c->cur;
     // sharded: a tick that needed a wide table keeps it for the next one while the fill
     // level stays beyond the narrow table (no relaunch per tick)
     if (c->shard) c->shard_R = c->last.fill_level + 2 > kRFused ? c->l_R : 0;
-    c->undo_E = 0;  // the tick's completed entries stay completed
     c->head = c->last.log_head;
     c->head_local += c->shard ? c->last.n_local : 0;
     c->Qtrue = c->last.queue_len;
     c->last_L = c->last.fill_level;
     c->last_O = c->last.n_orphans;
-    if (c->l_win) {
+    if (c->life.win) {
         // the queue stays in its buffers: the window slid and grew
         c->qoff = c->hout->win_head;
         c->Qn = c->hout->new_qlen;
@@ -2624,15 +2571,13 @@ int fb_tick_commit(fb_ctx *c) {
         c->Qn = c->last.queue_len;
         c->maxc_hint = std::max(1, c->last.max_free);
     }
-    c->launched = c->waited = false;
-    c->phase = 0;
+    life_commit(c->life, deferred, lazy_ctx(c) && c->last.n_orphans > 0);  // (lazy: its orphans stay in the log)
     return FB_OK;
 }
 
 int fb_get_local_assignments(fb_ctx *c, int64_t first, int64_t n, int64_t *task, int32_t *slot) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_local_assignments)) return rc_;
     if (first < 0 || n < 0 || first + n > c->last.n_local) return fail(c, FB_EINVAL, "assignment range");
     if (!n) return FB_OK;
     const int64_t base = c->shard ? c->l_head_local : c->l_head;
@@ -2695,7 +2640,7 @@ static int orph_out(fb_ctx *c, int64_t *dst, int64_t n) {
 // A window tick leaves its evicted slots to the per-slot status bytes: the ascending list
 // is built (once per tick) when something reads it.
 static int evict_ready(fb_ctx *c) {
-    if (!c->l_win || c->evict_ok || !c->last.n_evicted) return FB_OK;
+    if (!c->life.win || c->evict_ok || !c->last.n_evicted) return FB_OK;
     launch_evict_gather(c->evicted, c->st, c->wcnt, c->wpre, c->W, Stream(c->stream));
     HIPCHK(c, hipGetLastError());
     c->evict_ok = true;
@@ -2710,7 +2655,7 @@ static int copy_out(fb_ctx *c, void *dst, const void *src, size_t bytes) {
 
 int fb_get_assignments(fb_ctx *c, int64_t first, int64_t n, int32_t *dst) {
     if (!c || !dst) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_assignments)) return rc_;
     if (c->shard && !c->l_full)
         return fail(c, FB_ESTATE, "sharded context: use fb_get_local_assignments (or fb_set_full_assign)");
     if (first < 0 || n < 0 || first + n > c->last.n_assigned) return fail(c, FB_EINVAL, "assignment range");
@@ -2720,7 +2665,7 @@ int fb_get_assignments(fb_ctx *c, int64_t first, int64_t n, int32_t *dst) {
 
 int fb_get_orphans(fb_ctx *c, int64_t n, int64_t *dst) {
     if (!c || !dst) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_orphans)) return rc_;
     if (n < 0 || n > c->last.n_orphans_local) return fail(c, FB_EINVAL, "orphan count");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = orph_out(c, dst, n)) return rc;
@@ -2730,7 +2675,7 @@ int fb_get_orphans(fb_ctx *c, int64_t n, int64_t *dst) {
 
 int fb_get_evicted(fb_ctx *c, int32_t n, int32_t *dst) {
     if (!c || !dst) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_evicted)) return rc_;
     if (n < 0 || n > c->last.n_evicted) return fail(c, FB_EINVAL, "evicted count");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->l_cout) {  // the tick wrote them into the registered pinned buffer
@@ -2743,7 +2688,7 @@ int fb_get_evicted(fb_ctx *c, int32_t n, int32_t *dst) {
 
 int fb_get_outputs(fb_ctx *c, int32_t *assign, int64_t *orphans, int32_t *evicted) {
     if (!c) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_outputs)) return rc_;
     if (assign && c->shard) return fail(c, FB_ESTATE, "sharded context: use fb_get_local_assignments");
     HIPCHK(c, hipSetDevice(c->device));
     // the three copies back to back on the stream, one synchronisation
@@ -2763,10 +2708,8 @@ int fb_get_outputs(fb_ctx *c, int32_t *assign, int64_t *orphans, int32_t *evicte
 
 int fb_set_window(fb_ctx *c, int mode) {
     if (!c) return FB_EINVAL;
-    if (c->shard || c->deque) return fail(c, FB_ESTATE, "window ticks exist on one-GPU heartbeat contexts only");
     if (mode < -1 || mode > 1) return fail(c, FB_EINVAL, "window mode %d (-1 auto, 0 off, 1 on)", mode);
-    if (c->launched) return fail(c, FB_ESTATE, "fb_set_window between ticks only");
-    if (int rc = flush_commit(c)) return rc;
+    if (int rc_ = enter(c, Call::set_window)) return rc_;
     if (mode > 0) {
         if (int rc = win_alloc(c)) return rc;
     }
@@ -2776,7 +2719,7 @@ int fb_set_window(fb_ctx *c, int mode) {
 
 int fb_set_eager_commit(fb_ctx *c, int enable) {
     if (!c) return FB_EINVAL;
-    if (c->launched && !c->waited) return fail(c, FB_ESTATE, "fb_set_eager_commit with a tick in flight");
+    if (int rc_ = enter(c, Call::set_eager_commit)) return rc_;
     c->eager = enable ? 1 : 0;
     return FB_OK;
 }
@@ -2791,8 +2734,7 @@ int fb_window_stats(fb_ctx *c, int64_t *window_ticks, int64_t *fallbacks) {
 int fb_set_compact_out(fb_ctx *c, int32_t *slot, uint8_t *cnt, int64_t cap, int64_t *orphans, int64_t ocap,
                        int32_t *evicted, int64_t ecap) {
     if (!c) return FB_EINVAL;
-    if (c->shard) return fail(c, FB_ESTATE, "compact assignments exist on one-GPU contexts only");
-    if (c->launched && !c->waited) return fail(c, FB_ESTATE, "fb_set_compact_out with a tick in flight");
+    if (int rc_ = enter(c, Call::set_compact_out)) return rc_;
     if (!slot) {  // unregister
         c->cout_slot = nullptr;
         return FB_OK;
@@ -2830,7 +2772,7 @@ int fb_set_compact(fb_ctx *c, int enable) {
 int fb_get_outputs_compact(fb_ctx *c, int32_t *slot, uint8_t *cnt, int64_t cap, int64_t *n_pos, int64_t *orphans,
                            int32_t *evicted) {
     if (!c || !n_pos) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_outputs_compact)) return rc_;
     if (!c->l_compact) return fail(c, FB_ESTATE, "the tick was launched without fb_set_compact");
     if (c->last.fill_level + 1 > 255)
         return fail(c, FB_ERANGE, "fill level %d: rounds beyond a byte, read fb_get_outputs", c->last.fill_level);
@@ -2904,7 +2846,7 @@ int fb_get_outputs_compact(fb_ctx *c, int32_t *slot, uint8_t *cnt, int64_t cap, 
 // so they are expanded in parallel (FAASBAL_EXPAND_THREADS workers, default 8).
 int fb_expand_compact(fb_ctx *c, const int32_t *slot, const uint8_t *cnt, int64_t n_pos, int32_t *assign) {
     if (!c || (n_pos && (!slot || !cnt)) || (!assign && c->last.n_assigned)) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::expand_compact)) return rc_;
     const int L = c->last.fill_level;
     const int64_t N = c->last.n_assigned;
     if (L + 1 > 255) return fail(c, FB_ERANGE, "fill level %d beyond the compact form", L);
@@ -2955,7 +2897,7 @@ int fb_host_free(fb_ctx *c, void *ptr) {
 
 int fb_get_event_status(fb_ctx *c, int32_t n, uint8_t *dst) {
     if (!c || !dst) return FB_EINVAL;
-    if (!c->waited) return fail(c, FB_ESTATE, "no waited tick");
+    if (int rc_ = enter(c, Call::get_event_status)) return rc_;
     if (n < 0 || n > c->l_E) return fail(c, FB_EINVAL, "event count");
     const uint8_t *src = c->shard ? c->xbuf + xlayout(c->world, c->l_E, c->l_Qn + 2 * (int64_t)c->l_E).evs : c->ev_status;
     if (n) HIPCHK(c, hipMemcpy(dst, src, (size_t)n, hipMemcpyDeviceToHost));
@@ -3029,9 +2971,7 @@ int fb_tick(fb_ctx *c, double now, double tte, int32_t n_events, const uint8_t *
 
 int fb_device_view_get(fb_ctx *c, fb_device_view *v) {
     if (!c || !v) return FB_EINVAL;
-    if (int rc_ = win_uncommitted(c, "fb_device_view_get")) return rc_;
-    if (int rc_ = flush_commit(c)) return rc_;
-    if (int rc_ = log_undo_failed(c, true)) return rc_;  // a failed launch's in-place clears
+    if (int rc_ = enter(c, Call::device_view)) return rc_;
     v->free_processes = &c->free_[c->cur]->x;
     v->free_processes_stride = (int32_t)sizeof(int2);
     v->last_heartbeat = c->hb;
@@ -3044,7 +2984,7 @@ int fb_device_view_get(fb_ctx *c, fb_device_view *v) {
     if (int rc_ = log_settle(c)) return rc_;
     v->log_slot = c->log_slot;
     v->orphans = orph_dense_dev(c);
-    if (c->waited) {
+    if (life_waited(c->life)) {
         if (int rc = evict_ready(c)) return rc;
         HIPCHK(c, stream_wait(c));
     }
@@ -3057,27 +2997,25 @@ int fb_device_view_get(fb_ctx *c, fb_device_view *v) {
 
 int fb_set_full_assign(fb_ctx *c, int on) {
     if (!c) return FB_EINVAL;
-    if (c->launched) return fail(c, FB_ESTATE, "fb_set_full_assign between ticks only");
-    if (!c->shard) return fail(c, FB_ESTATE, "fb_set_full_assign on a one-GPU context (it always has them)");
+    if (int rc_ = enter(c, Call::set_full_assign)) return rc_;
     c->full_assign = on ? 1 : 0;
     return FB_OK;
 }
 
 int fb_set_round_hint(fb_ctx *c, int32_t max_free) {
     if (!c) return FB_EINVAL;
-    if (c->launched) return fail(c, FB_ESTATE, "fb_set_round_hint between ticks only");
+    if (int rc_ = enter(c, Call::set_round_hint)) return rc_;
     c->maxc_hint = std::max<int32_t>(1, max_free);
     return FB_OK;
 }
 
 int fb_set_path(fb_ctx *c, const char *name, int value) {
     if (!c || !name) return FB_EINVAL;
-    if (c->launched) return fail(c, FB_ESTATE, "fb_set_path between ticks only");
-    if (int rc_ = flush_commit(c)) return rc_;
+    if (int rc_ = enter(c, Call::set_path)) return rc_;
     for (const PathKnob &k : kPathKnobs) {
         if (strcmp(name, k.name) || !knob_allows(k, value)) continue;
         // "lazy" off: the entries left so far leave the log first
-        if (k.member == &PathKnobs::lazy_on && !value && c->stale_any)
+        if (k.member == &PathKnobs::lazy_on && !value)
             if (int rc_ = log_settle(c)) return rc_;
         c->paths.*k.member = value;
         return FB_OK;
@@ -3200,7 +3138,7 @@ int fb_selftest(fb_ctx *c, int32_t *errors) {
 // Diagnostic: copy the stamp buffer (meaningful only in FAASBAL_STAMPS builds).
 int fb_debug_read(fb_ctx *c, unsigned long long *dst, int64_t n, int64_t *n_total) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
+    if (int rc_ = enter(c, Call::debug_read)) return rc_;
     HIPCHK(c, stream_wait(c));
     if (n_total) *n_total = (int64_t)c->dbg_n;
     if (dst && n > 0) HIPCHK(c, hipMemcpy(dst, c->dbg, (size_t)std::min<int64_t>(n, c->dbg_n) * 8, hipMemcpyDeviceToHost));
@@ -3209,7 +3147,7 @@ int fb_debug_read(fb_ctx *c, unsigned long long *dst, int64_t n, int64_t *n_tota
 
 int fb_sync(fb_ctx *c) {
     if (!c) return FB_EINVAL;
-    if (int rc_ = flush_commit(c)) return rc_;
+    if (int rc_ = enter(c, Call::sync)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, stream_wait(c));
     return FB_OK;

@@ -18,7 +18,7 @@ def build_lib(verbose=False, out=None, defines=()):
     OUT_ = out or OUT
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "faasbal_kernels.h"), os.path.join(CSRC, "faasbal_plan.h"),
-            os.path.join(CSRC, "faasbal_layout.h"),
+            os.path.join(CSRC, "faasbal_layout.h"), os.path.join(CSRC, "faasbal_life.h"),
             os.path.join(REPO, "include", "faasbal.h")]
     stamp = OUT_ + ".defines"
     want = " ".join(sorted(defines))

@@ -27,7 +27,8 @@ extern "C" {
 #define FB_EHIP (-3)    /* HIP runtime error                                  */
 #define FB_ERANGE (-4)  /* free counts beyond the supported round range       */
 #define FB_ENOSPC (-5)  /* in-flight log full                                 */
-#define FB_ESTATE (-6)  /* call out of order (e.g. wait without launch)       */
+#define FB_ESTATE (-6)  /* call out of order (e.g. wait without launch): DESIGN.md §5f,
+                         * "The life of a tick", has every call at every point of a tick */
 #define FB_ERERUN (-7)  /* sharded: the fill level reached the round table; launch the
                          * same tick again (a wider table), exchange, continue, wait */
 
@@ -117,11 +118,9 @@ int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
  * expect_kept >= 0: if the live count differs, FB_ESTATE and nothing changes (a host mirror that
  * disagrees).  cap < live count with kept_seq != NULL: FB_EINVAL and nothing changes.
  * FB_ESTATE also: a sharded context (its sequence numbers are global across ranks: compacting
- * them needs a collective), staged events pending, a tick launched but not waited, or waited
- * but not committed.  A tick whose fb_tick_wait failed with FB_ENOSPC is discarded (launch it
- * again with the new sequences), as fb_load_state discards it: on every context kind the
- * entries its results named count as live and are kept (a context that completed them in
- * place at launch names them again before it counts).
+ * them needs a collective), and out of order.  A tick whose fb_tick_wait failed
+ * with FB_ENOSPC is discarded (launch it again with the new sequences), as fb_load_state
+ * discards it: on every context kind the entries its results named count as live and are kept.
  * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
 int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept);
 
@@ -138,8 +137,8 @@ int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t 
  * are NaN, dispatchable is -1, and n_queued counts tokens with repetition.
  * FB_EINVAL: out == NULL, n_edges outside [0, FB_PS_MAX_EDGES], and on heartbeat contexts edges
  * not finite and strictly ascending or a non-finite now or tte.  FB_ESTATE: a sharded context
- * (its pool is the group's, which needs a collective), staged events pending, a tick launched
- * but not committed.  A refused call changes nothing.
+ * (its pool is the group's, which needs a collective), and out of order.  A
+ * refused call changes nothing.
  * Replaces nothing in the reference, which keeps no such view: its only look at the pool is
  * the per-worker is_alive walk of purge_workers (task_dispatcher.py:241-249). */
 #define FB_PS_FREE_BINS 33
