@@ -652,8 +652,7 @@ int log_undo(fb_ctx *c) {
 }
 
 // The top of every entry point: life_gate's refusal, or the duties it names, in order.
-int enter(fb_ctx *c, Call call) {
-    const Gate g = life_gate(c->life, c->caps, call);
+int enter(fb_ctx *c, const Gate &g) {
     if (g.duties & kFlush)
         if (int rc_ = flush_commit(c)) return rc_;
     if (g.refuse) return fail(c, FB_ESTATE, "%s", g.refuse);
@@ -662,6 +661,7 @@ int enter(fb_ctx *c, Call call) {
     if (g.duties & kUndoSync) HIPCHK(c, stream_wait(c));
     return FB_OK;
 }
+int enter(fb_ctx *c, Call call) { return enter(c, life_gate(c->life, c->caps, call)); }
 
 // Whether the tick about to launch (c->l_*) runs as a window tick: plan_window's rules on
 // this context's state; c->l_nchW, the window chunks it scans.
@@ -1826,9 +1826,13 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
 // The committed pool summarised on the device.  The three launches write only
 // the scratch and the host-mapped record; nothing here settles the log or normalises a window,
 // so the ticks after it make the launches they would have made without it.
-int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, int32_t n_edges, fb_pool_summary *out) {
+// shard: a rank's part for fb_pool_stats_shard (its own slots and log shard, the replicated
+// queue's positions on its slots; *queue_len the queue's length).
+static int pool_stats_run(fb_ctx *c, bool shard, double now, double tte, const double *age_edges, int32_t n_edges,
+                          fb_pool_summary *out, int64_t *queue_len) {
     if (!c) return FB_EINVAL;
-    if (!out) return fail(c, FB_EINVAL, "fb_pool_stats: out is null");
+    if (!out) return fail(c, FB_EINVAL, "%s: out is null", shard ? "fb_pool_stats_shard" : "fb_pool_stats");
+    if (shard && !queue_len) return fail(c, FB_EINVAL, "fb_pool_stats_shard: queue_len is null");
     if (n_edges < 0 || n_edges > FB_PS_MAX_EDGES)
         return fail(c, FB_EINVAL, "n_edges %d outside [0, %d]", n_edges, FB_PS_MAX_EDGES);
     const bool hbc = !c->deque;  // liveness exists
@@ -1841,7 +1845,8 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
         if (!std::isfinite(now) || !std::isfinite(tte))
             return fail(c, FB_EINVAL, "now %g / tte %g must be finite", now, tte);
     }
-    if (int rc_ = enter(c, Call::pool_stats)) return rc_;  // (its flush: observably an immediate commit)
+    // (its flush: observably an immediate commit)
+    if (int rc_ = shard ? enter(c, life_gate_pool_stats_shard(c->life, c->caps)) : enter(c, Call::pool_stats)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->ps_out) {
         if (hipHostMalloc((void **)&c->ps_out, kPsCols * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
@@ -1851,7 +1856,8 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
         }
         HIPCHK(c, hipHostGetDevicePointer((void **)&c->ps_out_dev, c->ps_out, 0));
     }
-    const PsPlan p = ps_plan(c->W, c->Qn, c->head);
+    const int64_t head = shard ? c->head_local : c->head;  // the entries this context's log holds
+    const PsPlan p = ps_plan(c->W, c->Qn, head);
     if (p.bytes > c->ps_cap) {
         // sized for this state, doubling, never beyond a full table, queue and log
         const size_t full = ps_plan(c->W_cap, std::max<int64_t>(c->qcap, c->Wq_cap), c->log_cap).bytes;
@@ -1875,10 +1881,13 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     a.nt = p.nt;
     a.hb_chk = hbc ? 1 : 0;
     a.tomb_chk = c->win_cap ? 1 : 0;
+    // (a sharded Life is never stale: only contexts with message lists commit lazily,
+    // fb_tick_commit, and a sharded context has none -- its entries are completed in place)
     a.live_chk = c->life.stale ? 1 : 0;
+    a.slot_base = shard ? c->slot_base : 0;
     a.Qn = c->Qn;
     a.qoff = c->qoff;
-    a.head = c->head;
+    a.head = head;
     a.reg = c->reg;
     a.free_ = c->free_[c->cur];
     a.hb = c->hb;
@@ -1894,11 +1903,11 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     a.out = c->ps_out_dev;
     if (p.slots.grid() > 0) {
         Timer t(c, "ps_slots");
-        launch_ps_slots(a, t.st());
+        shard ? launch_ps_slots_shard(a, t.st()) : launch_ps_slots(a, t.st());
     }
     if (p.log_grid > 0) {
         Timer t(c, "ps_log");
-        launch_ps_log(a, t.st());
+        shard ? launch_ps_log_shard(a, t.st()) : launch_ps_log(a, t.st());
     }
     {
         Timer t(c, "ps_fold");
@@ -1914,12 +1923,15 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     if (n_exp < 0 || n_exp > n_reg)
         return fail(c, FB_EHIP, "device-reported expired slots %lld outside [0, %lld] (registered)", (long long)n_exp,
                     (long long)n_reg);
-    if (r[kPsQ] < 0 || r[kPsQExp] < 0 || r[kPsQ] + r[kPsQExp] != c->Qtrue)
+    if (shard && (r[kPsQ] < 0 || r[kPsQExp] < 0 || r[kPsQ] + r[kPsQExp] > c->Qn))
+        return fail(c, FB_EHIP, "device-reported queue positions %lld + %lld outside [0, %lld] (the queue's length)",
+                    (long long)r[kPsQ], (long long)r[kPsQExp], (long long)c->Qn);
+    if (!shard && (r[kPsQ] < 0 || r[kPsQExp] < 0 || r[kPsQ] + r[kPsQExp] != c->Qtrue))
         return fail(c, FB_EHIP, "device-reported queue positions %lld + %lld differ from the queue's %lld", (long long)r[kPsQ],
                     (long long)r[kPsQExp], (long long)c->Qtrue);
-    if (r[kPsLive] < 0 || r[kPsLiveExp] < 0 || r[kPsLive] + r[kPsLiveExp] > c->head)
-        return fail(c, FB_EHIP, "device-reported live entries %lld + %lld outside [0, %lld] (log head)", (long long)r[kPsLive],
-                    (long long)r[kPsLiveExp], (long long)c->head);
+    if (r[kPsLive] < 0 || r[kPsLiveExp] < 0 || r[kPsLive] + r[kPsLiveExp] > head)
+        return fail(c, FB_EHIP, "device-reported live entries %lld + %lld outside [0, %lld] (%s)", (long long)r[kPsLive],
+                    (long long)r[kPsLiveExp], (long long)head, shard ? "the log shard's entries" : "log head");
     int64_t fsum = 0, asum = 0;
     for (int i = 0; i < FB_PS_FREE_BINS; ++i) fsum += r[kPsFreeHist + i];
     for (int i = 0; i <= FB_PS_MAX_EDGES; ++i) asum += r[kPsAgeHist + i];
@@ -1947,6 +1959,59 @@ int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, in
     if (!any_hb) s.oldest_hb = s.newest_hb = __builtin_nan("");
     for (int i = 0; i < FB_PS_FREE_BINS; ++i) s.free_hist[i] = r[kPsFreeHist + i];
     for (int i = 0; i <= FB_PS_MAX_EDGES; ++i) s.age_hist[i] = r[kPsAgeHist + i];
+    *out = s;
+    if (queue_len) *queue_len = c->Qn;
+    return FB_OK;
+}
+
+int fb_pool_stats(fb_ctx *c, double now, double tte, const double *age_edges, int32_t n_edges, fb_pool_summary *out) {
+    return pool_stats_run(c, false, now, tte, age_edges, n_edges, out, nullptr);
+}
+
+int fb_pool_stats_shard(fb_ctx *c, double now, double tte, const double *age_edges, int32_t n_edges,
+                        fb_pool_summary *part, int64_t *queue_len) {
+    return pool_stats_run(c, true, now, tte, age_edges, n_edges, part, queue_len);
+}
+
+// The ranks' parts folded into the group's summary: host arithmetic only (no device, no
+// lifecycle: the parts are the caller's).
+int fb_pool_merge(fb_ctx *c, const fb_pool_summary *parts, const int64_t *queue_lens, int32_t n_parts,
+                  fb_pool_summary *out) {
+    if (n_parts < 1) return fail(c, FB_EINVAL, "fb_pool_merge: n_parts %d < 1", n_parts);
+    if (!parts || !queue_lens || !out) return fail(c, FB_EINVAL, "fb_pool_merge: a null pointer");
+    fb_pool_summary s{};
+    s.log_head = parts[0].log_head;
+    s.oldest_hb = s.newest_hb = __builtin_nan("");
+    bool no_counts = false;
+    for (int p = 0; p < n_parts; ++p) {
+        const fb_pool_summary &x = parts[p];
+        if (x.log_head != s.log_head)
+            return fail(c, FB_EINVAL, "fb_pool_merge: part %d has log head %lld, part 0 %lld", p, (long long)x.log_head,
+                        (long long)s.log_head);
+        if (queue_lens[p] != queue_lens[0])
+            return fail(c, FB_EINVAL, "fb_pool_merge: part %d has queue length %lld, part 0 %lld", p,
+                        (long long)queue_lens[p], (long long)queue_lens[0]);
+        s.n_slots += x.n_slots;
+        s.n_registered += x.n_registered;
+        s.n_expired += x.n_expired;
+        s.n_queued += x.n_queued;
+        s.n_queued_expired += x.n_queued_expired;
+        s.dispatchable += x.dispatchable;
+        s.free_total += x.free_total;
+        s.inflight += x.inflight;
+        s.inflight_expired += x.inflight_expired;
+        no_counts = no_counts || x.inflight_max < 0;
+        s.inflight_max = std::max(s.inflight_max, x.inflight_max);
+        // (NaN: a part without a heartbeat; the comparisons skip it)
+        if (x.oldest_hb == x.oldest_hb && !(s.oldest_hb <= x.oldest_hb)) s.oldest_hb = x.oldest_hb;
+        if (x.newest_hb == x.newest_hb && !(s.newest_hb >= x.newest_hb)) s.newest_hb = x.newest_hb;
+        for (int i = 0; i < FB_PS_FREE_BINS; ++i) s.free_hist[i] += x.free_hist[i];
+        for (int i = 0; i <= FB_PS_MAX_EDGES; ++i) s.age_hist[i] += x.age_hist[i];
+    }
+    if (no_counts) s.inflight_max = -1;
+    if (s.n_queued + s.n_queued_expired != queue_lens[0])
+        return fail(c, FB_EINVAL, "fb_pool_merge: the parts hold %lld + %lld queue positions, the queue %lld",
+                    (long long)s.n_queued, (long long)s.n_queued_expired, (long long)queue_lens[0]);
     *out = s;
     return FB_OK;
 }

@@ -597,7 +597,7 @@ struct PsArgs {
     int n_edges;
     int W, nt;                   // slots, log tiles
     int hb_chk, tomb_chk, live_chk;
-    int64_t Qn, qoff, head;      // the committed queue is [qoff, qoff + Qn) of queue / qfree
+    int64_t Qn, qoff, head;      // the committed queue is [qoff, qoff + Qn) of queue / qfree (sharded: head_local)
     const uint8_t *reg;
     const int2 *free_;
     const double *hb;
@@ -608,9 +608,15 @@ struct PsArgs {
     unsigned long long *xbits;   // [cdiv(W, 64)] the expired bitmap: k_ps_slots writes, k_ps_log reads
     int64_t *srow, *qrow, *lrow;  // a partial row per workgroup of the slot, queue and log roles
     int64_t *out;                // [kPsCols] the folded record (host-mapped memory)
+    // the sharded variants only (last, so that the one-GPU kernels' argument offsets stay):
+    int slot_base;               // the rank's first global slot (W: its own slots)
 };
 void launch_ps_slots(const PsArgs &a, Stream st);
 void launch_ps_log(const PsArgs &a, Stream st);
 void launch_ps_fold(const PsArgs &a, Stream st);
+// a rank's part (fb_pool_stats_shard): the queue positions and log entries of slots
+// [slot_base, slot_base + W), over ps_plan(W, Qn, head_local); the fold is the same
+void launch_ps_slots_shard(const PsArgs &a, Stream st);
+void launch_ps_log_shard(const PsArgs &a, Stream st);
 
 }  // namespace fb

@@ -5191,6 +5191,10 @@ __global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
 // fb_pool_stats (layout: ps_plan, faasbal_layout.h): reductions and two small histograms over
 // the committed arrays, read only.  Every load is unconditional at a clamped index and masked
 // afterwards; every workgroup writes its whole partial row (no global atomics).
+// kShard (fb_pool_stats_shard): a rank's part.  The tables hold the rank's W slots, the queue
+// is the group's and the log shard names global slots: both are rebased by slot_base, and a
+// queue position counts only where the rebased slot is one of the rank's.  The one-GPU
+// instantiation reads no slot_base.
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -5219,6 +5223,7 @@ __device__ __forceinline__ unsigned long long ps_col_fold(int c, unsigned long l
          : c == kPsHbMax ? (unsigned long long)__double_as_longlong(fmax(da, dv)) : acc + v;
 }
 
+template <bool kShard>
 __global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
     prefetch_args(a);
     __shared__ uint32_t hist[kWaves][64];                     // per wave: free bins, then age bins
@@ -5236,6 +5241,7 @@ __global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
         for (int k = 0; k < kPsTiles; ++k) {
             const int64_t p = p0 + (int64_t)k * kBS;
             s[k] = a.queue[a.qoff + (p < a.Qn ? p : a.Qn - 1)];
+            if (kShard) s[k] -= a.slot_base;  // (another rank's slot: outside [0, W), masked below)
         }
         if (a.tomb_chk) {
 #pragma unroll
@@ -5257,7 +5263,8 @@ __global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
         unsigned long long disp = 0;
 #pragma unroll
         for (int k = 0; k < kPsTiles; ++k) {
-            const bool valid = p0 + (int64_t)k * kBS < a.Qn && qf[k] != kTomb;
+            const bool own = !kShard || (uint32_t)s[k] < (uint32_t)a.W;
+            const bool valid = p0 + (int64_t)k * kBS < a.Qn && qf[k] != kTomb && own;
             const bool exp = a.hb_chk && (a.now - h[k]) > a.tte;
             nq += (uint32_t)__popcll(__ballot(valid && !exp));
             nqe += (uint32_t)__popcll(__ballot(valid && exp));
@@ -5367,7 +5374,11 @@ __global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
 }
 
 // A wave per tile as k_lc_flag; a live entry's slot is looked up in the expired bitmap
-// k_ps_slots wrote (hb_chk), the gathers branch-free at a clamped slot.
+// k_ps_slots wrote (hb_chk), the gathers branch-free at a clamped slot.  kShard: the log is
+// the rank's shard (head: its entries), whose entries name global slots; no sharded context
+// leaves completed entries in the log (live_chk is never set: its test compares an entry's
+// index, which a shard's entries do not carry).
+template <bool kShard>
 __global__ __launch_bounds__(kBS) void k_ps_log(PsArgs a) {
     prefetch_args(a);
     __shared__ uint32_t wc[kWaves][kPsLCols];
@@ -5388,8 +5399,12 @@ __global__ __launch_bounds__(kBS) void k_ps_log(PsArgs a) {
                 s[k] = a.log[q < a.head ? q : a.head - 1];
             }
 #pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) sc[k] = s[k] < 0 ? 0 : (s[k] > wlast ? wlast : s[k]);
-            if (a.live_chk) {
+            for (int k = 0; k < kLcBatch; ++k) {
+                // (a completed entry, -1, stays negative: slot_base >= 0)
+                if (kShard) s[k] = s[k] < 0 ? s[k] : s[k] - a.slot_base;
+                sc[k] = s[k] < 0 ? 0 : (s[k] > wlast ? wlast : s[k]);
+            }
+            if (!kShard && a.live_chk) {
 #pragma unroll
                 for (int k = 0; k < kLcBatch; ++k) {
                     r[k] = a.reg[sc[k]];
@@ -5412,7 +5427,7 @@ __global__ __launch_bounds__(kBS) void k_ps_log(PsArgs a) {
 #pragma unroll
             for (int k = 0; k < kLcBatch; ++k) {
                 const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-                const bool live = q < a.head && s[k] >= 0 && r[k] && (uint64_t)q >= (uint64_t)e[k];
+                const bool live = q < a.head && s[k] >= 0 && (!kShard || s[k] < a.W) && r[k] && (uint64_t)q >= (uint64_t)e[k];
                 const bool exp = (xw[k] >> (sc[k] & 63)) & 1ull;
                 nl += (uint32_t)__popcll(__ballot(live && !exp));
                 nle += (uint32_t)__popcll(__ballot(live && exp));
@@ -5586,11 +5601,19 @@ void launch_lc_move(const LcArgs &a, Stream st) {
 }
 void launch_ps_slots(const PsArgs &a, Stream st) {
     const PsPlan p = ps_plan(a.W, a.Qn, a.head);
-    if (p.slots.grid() > 0) hipExtLaunchKernelGGL(k_ps_slots, dim3(p.slots.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+    if (p.slots.grid() > 0) hipExtLaunchKernelGGL(k_ps_slots<false>, dim3(p.slots.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_ps_log(const PsArgs &a, Stream st) {
     const PsPlan p = ps_plan(a.W, a.Qn, a.head);
-    if (p.log_grid > 0) hipExtLaunchKernelGGL(k_ps_log, dim3(p.log_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+    if (p.log_grid > 0) hipExtLaunchKernelGGL(k_ps_log<false>, dim3(p.log_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_ps_slots_shard(const PsArgs &a, Stream st) {
+    const PsPlan p = ps_plan(a.W, a.Qn, a.head);
+    if (p.slots.grid() > 0) hipExtLaunchKernelGGL(k_ps_slots<true>, dim3(p.slots.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_ps_log_shard(const PsArgs &a, Stream st) {
+    const PsPlan p = ps_plan(a.W, a.Qn, a.head);
+    if (p.log_grid > 0) hipExtLaunchKernelGGL(k_ps_log<true>, dim3(p.log_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_ps_fold(const PsArgs &a, Stream st) {
     const PsPlan p = ps_plan(a.W, a.Qn, a.head);

@@ -178,6 +178,18 @@ inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     return no("unknown call");
 }
 
+// fb_pool_stats_shard, a rank's part of its group's summary: fb_pool_stats' gate on the rank
+// with the sharded refusal lifted -- the same refusals at every point of a tick, the same
+// flush and undo -- and a refusal of its own where fb_pool_stats answers.  (No Call of its
+// own: it is that call's place in a tick's life.)
+inline Gate life_gate_pool_stats_shard(const Life &l, const CtxCaps &k) {
+    if (!k.sharded)
+        return Gate{"fb_pool_stats_shard on a one-GPU context: use fb_pool_stats", l.cm_pending ? (unsigned)kFlush : 0u};
+    CtxCaps one = k;
+    one.sharded = false;
+    return life_gate(l, one, Call::pool_stats);
+}
+
 // The second gate, where a log pointer or copy is handed out: the deferred clears of the
 // entries lazy commits left, all at once (after the flush above).
 inline bool life_settle_due(const Life &l) { return l.stale; }

@@ -467,9 +467,11 @@ class GpuPushDispatcher:
         heartbeat age (``age_edges``, default a quarter, half, three quarters and the whole of
         ``time_to_expire``) -- plus the host's own figures: ``pending``, ``inflight_host``,
         ``ticks``, ``compactions`` and ``log_garbage`` (log entries that are not live).  A
-        balancer with ``pool_stats`` (a one-GPU ``GpuBalancer``: fb_pool_stats) computes it on
-        the device, a few hundred bytes back and the tick pipeline untouched; otherwise (shard
-        groups) the whole state is read and summarised by ``faasbal.poolstats``."""
+        balancer with ``pool_stats`` (a one-GPU ``GpuBalancer``: fb_pool_stats; a shard group:
+        every rank's fb_pool_stats_shard, merged) computes it on the device, a few hundred
+        bytes back per rank and the tick pipeline untouched -- a shard group's without
+        ``inflight_max`` (-1).  Otherwise (balancers without a device summary, such as test
+        doubles) the whole state is read and summarised by ``faasbal.poolstats``."""
         tte = float(self.time_to_expire)
         if age_edges is None:
             age_edges = tuple(tte * f for f in (0.25, 0.5, 0.75, 1.0))

@@ -24,6 +24,7 @@ import numpy as np
 from . import _lib
 from .balancer import GpuBalancer, _arr, _p
 from ._lib import FB_ERERUN, FaasbalError
+from .poolstats import HISTS, SCALARS, merge_summaries
 
 MAX_RELAUNCH = 6  # FB_ERERUN: each relaunch at least doubles the round table
 
@@ -81,9 +82,23 @@ class ShardedBalancer(GpuBalancer):
 
     # fb_log_compact refuses sharded contexts (sequence numbers are global across ranks)
     compact_log = None
-    # fb_pool_stats too (the pool is the group's: a summary needs a collective); shard groups
-    # take GpuPushDispatcher.pool_stats' host path
+    # fb_pool_stats too: a rank cannot answer for the group.  Its part is pool_stats_part;
+    # ShardGroup.pool_stats gathers and merges the ranks' parts
     pool_stats = None
+
+    def pool_stats_part(self, now, tte, age_edges=()):
+        """fb_pool_stats_shard: this rank's part of the group's pool summary as
+        ``(dict, queue_len)`` -- the dict as ``GpuBalancer.pool_stats`` returns it, over this
+        rank's slots, its log shard and the replicated queue's positions on its slots
+        (``poolstats.merge_summaries`` folds the ranks' parts).  Reads only; between ticks."""
+        edges = _arr(age_edges, np.float64).reshape(-1)
+        out, qn = _lib.PoolSummary(), C.c_int64()
+        self._chk(self.lib.fb_pool_stats_shard(self.h, float(now), float(tte), _p(edges), len(edges), C.byref(out),
+                                               C.byref(qn)))
+        d = {k: getattr(out, k) for k, _ in out._fields_[:-2]}
+        d["free_hist"] = np.array(out.free_hist, np.int64)
+        d["age_hist"] = np.array(out.age_hist, np.int64)
+        return d, qn.value
 
     def load(self, st):
         """Load this rank's part of a global state dict."""
@@ -225,11 +240,27 @@ class ShardGroup:
 
     mode = "heartbeat"
 
-    def __init__(self, n_workers):
+    def __init__(self, n_workers, rank_balancers=()):
         self.n_workers_global = int(n_workers)
+        # rank balancers (those this process holds) without a part of the summary, such as
+        # test doubles: no device summary, and GpuPushDispatcher.pool_stats reads the state
+        if not all(callable(getattr(b, "pool_stats_part", None)) for b in rank_balancers):
+            self.pool_stats = None
 
     def _each(self, op, **kw):  # -> list of per-rank results, rank order
         raise NotImplementedError
+
+    def pool_stats(self, now, tte, age_edges=()):
+        """The group's pool summary (``GpuBalancer.pool_stats``' dict): every rank's part,
+        computed where its shard lives, merged here.  ``inflight_max`` is -1: sharded
+        contexts keep no per-slot counts."""
+        edges = np.asarray(age_edges, np.float64).reshape(-1)
+        parts = self._each("stats", now=float(now), tte=float(tte), age_edges=edges)
+        out = merge_summaries([p for p, _ in parts], [q for _, q in parts])
+        if out["n_slots"] != self.n_workers_global:
+            raise FaasbalError(_lib.FB_ESTATE, "the ranks' parts cover %d slots, the table has %d"
+                               % (out["n_slots"], self.n_workers_global))
+        return out
 
     def load_state(self, reg, free, hb, epoch=None, queue=(), log=()):
         W = len(reg)
@@ -284,6 +315,8 @@ def serve_op(bal, op, kw, allreduce=None, commit=True):
         return out
     if op == "purge":
         return bal.purge(kw["now"], kw["tte"], allreduce=allreduce, commit=commit)
+    if op == "stats":  # (reads only: nothing to commit, nothing to settle)
+        return bal.pool_stats_part(kw["now"], kw["tte"], kw["age_edges"])
     raise ValueError("unknown group operation %r" % op)
 
 
@@ -312,9 +345,36 @@ def _settle(bal, op, outs):
 # gathered: every rank commits only when all succeeded) plus one padded byte tensor
 # per rank gathered to rank 0 (tasks, slots, orphans, evicted).  Loads and state reads
 # (not per tick) and failure messages travel as pickled objects.
-_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5}
+# A pool summary ("stats") travels as tensors too: the call header carries the number of
+# age edges in the event count's word and the clock and tte in theirs, the edges follow as
+# one float64 tensor when there are any, and every rank's part comes back as one fixed
+# int64 record (an ok flag, a code, the queue's length, then fb_pool_summary's words in
+# the struct's order, doubles as bit patterns), all-gathered so that every rank sees every
+# flag; only when a rank failed do the messages follow, pickled, as for ticks.
+_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6}
 _OP_NAMES = {v: k for k, v in _OP_CODES.items()}
 _HDR = 8  # int64 words of the call header / the per-rank result header
+_PS_WORDS = C.sizeof(_lib.PoolSummary) // 8  # fb_pool_summary's words (SCALARS' order, then HISTS')
+_PS_REC = 3 + _PS_WORDS
+_PS_DOUBLES = ("oldest_hb", "newest_hb")
+
+
+def _pack_summary(part, queue_len):
+    """A part as the stats record's words (ok = 1, code = 0)."""
+    w = [np.float64(part[k]).view(np.int64) if k in _PS_DOUBLES else np.int64(part[k]) for k in SCALARS]
+    return np.concatenate([np.array([1, 0, int(queue_len)], np.int64), np.array(w, np.int64)]
+                          + [np.asarray(part[k], np.int64) for k in HISTS])
+
+
+def _unpack_summary(rec):
+    """(part, queue_len) of an ok stats record."""
+    rec = np.ascontiguousarray(rec, np.int64)
+    body, n = rec[3:], len(SCALARS)
+    part = {k: float(body[i:i + 1].view(np.float64)[0]) if k in _PS_DOUBLES else int(body[i])
+            for i, k in enumerate(SCALARS)}
+    part["free_hist"] = body[n:n + _lib.PS_FREE_BINS].copy()
+    part["age_hist"] = body[n + _lib.PS_FREE_BINS:].copy()
+    return part, int(rec[2])
 
 
 def _dev(dist):
@@ -349,10 +409,17 @@ def _bcast_call(dist, dev, op, kw):
         h[2] = int(kw.get("n_pending", 0))
         h[3] = int(np.float64(kw["now"]).view(np.int64))
         h[4] = int(np.float64(kw["tte"]).view(np.int64))
+    elif op == "stats":
+        h[1] = len(kw["age_edges"])
+        h[3] = int(np.float64(kw["now"]).view(np.int64))
+        h[4] = int(np.float64(kw["tte"]).view(np.int64))
     dist.broadcast(h.to(dev), src=0)
     if op in ("tick", "purge"):
         if int(h[1]):
             dist.broadcast(torch.from_numpy(_pack_events(kw)).to(dev), src=0)
+    elif op == "stats":
+        if int(h[1]):
+            dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["age_edges"], np.float64)).to(dev), src=0)
     elif op != "stop":
         dist.broadcast_object_list([kw], src=0)
 
@@ -364,6 +431,12 @@ def _recv_call(dist, dev):
     dist.broadcast(h, src=0)
     h = h.cpu().numpy()
     op = _OP_NAMES[int(h[0])]
+    if op == "stats":
+        edges = torch.zeros(int(h[1]), dtype=torch.float64, device=dev)
+        if int(h[1]):
+            dist.broadcast(edges, src=0)
+        return op, dict(now=float(h[3:4].view(np.float64)[0]), tte=float(h[4:5].view(np.float64)[0]),
+                        age_edges=edges.cpu().numpy())
     if op not in ("tick", "purge"):
         if op == "stop":
             return op, {}
@@ -443,17 +516,49 @@ def _gather_results(dist, dev, op, guarded):
     return outs
 
 
+def _gather_stats(dist, dev, guarded):
+    """Every rank: its guarded part of a pool summary.  Returns, on every rank, the list of
+    (ok, (part, queue_len) | (code, message)) in rank order."""
+    import torch
+    ok, val = guarded
+    world = dist.get_world_size()
+    rec = np.zeros(_PS_REC, np.int64)
+    if ok:
+        rec = _pack_summary(*val)
+    else:
+        rec[1] = val[0] if val[0] is not None else 0
+    recs = [torch.zeros(_PS_REC, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(recs, torch.from_numpy(rec).to(dev))
+    recs = [x.cpu().numpy() for x in recs]
+    if not all(x[0] for x in recs):
+        msgs = [None] * world
+        dist.all_gather_object(msgs, None if ok else val)
+        return [(bool(x[0]), None if x[0] else msgs[i]) for i, x in enumerate(recs)]
+    return [(True, _unpack_summary(x)) for x in recs]
+
+
+def _gather(dist, dev, op, guarded):
+    """The ranks' guarded results of one operation, on every rank, in rank order."""
+    if op in ("tick", "purge"):
+        return _gather_results(dist, dev, op, guarded)
+    if op == "stats":
+        return _gather_stats(dist, dev, guarded)
+    outs = [None] * dist.get_world_size()
+    dist.all_gather_object(outs, guarded)
+    return outs
+
+
 class DistShardGroup(ShardGroup):
     """Rank 0's view of a table sharded over a torch.distributed group (one process
     per GPU): every call is broadcast to the ranks (serve_shard() runs on the
     others), each rank runs it on its own shard -- ticks with the exchange
     all-reduce over the group's backend (RCCL over xGMI for ``nccl``) -- and the
     per-rank results come back to rank 0.  Ticks and purges travel as tensors (the
-    event batch in one broadcast, the results in one gather); loads and state reads
-    as pickled objects."""
+    event batch in one broadcast, the results in one gather) and so do pool summaries (one
+    fixed record per rank); loads and state reads as pickled objects."""
 
     def __init__(self, balancer, n_workers):
-        super().__init__(n_workers)
+        super().__init__(n_workers, (balancer,))
         import torch.distributed as dist
         self.dist, self.bal = dist, balancer
         if dist.get_rank() != 0:
@@ -465,11 +570,7 @@ class DistShardGroup(ShardGroup):
     def _each(self, op, **kw):
         _bcast_call(self.dist, self.dev, op, kw)
         guarded = _serve_guarded(self.bal, op, kw)
-        if op in ("tick", "purge"):
-            outs = _gather_results(self.dist, self.dev, op, guarded)
-        else:
-            outs = [None] * self.dist.get_world_size()
-            self.dist.all_gather_object(outs, guarded)
+        outs = _gather(self.dist, self.dev, op, guarded)
         bad = _settle(self.bal, op, outs)
         if bad is not None:
             code, msg = bad
@@ -491,11 +592,7 @@ def serve_shard(balancer):
         if op == "stop":
             return
         guarded = _serve_guarded(balancer, op, kw)
-        if op in ("tick", "purge"):
-            outs = _gather_results(dist, dev, op, guarded)
-        else:
-            outs = [None] * dist.get_world_size()
-            dist.all_gather_object(outs, guarded)
+        outs = _gather(dist, dev, op, guarded)
         _settle(balancer, op, outs)  # rank 0 raises a failure; this rank keeps serving
 
 
@@ -505,9 +602,9 @@ class LocalShardGroup(ShardGroup):
     across GPUs, byte for byte (one contributor per byte)."""
 
     def __init__(self, world, n_workers, max_log, max_events=65536, device=0, rank_factory=None):
-        super().__init__(n_workers)
         make = rank_factory or (lambda r: ShardedBalancer(r, world, n_workers, max_log, max_events, device))
         self.bals = [make(r) for r in range(world)]
+        super().__init__(n_workers, self.bals)
 
     def _each(self, op, **kw):
         if op in ("tick", "purge"):

@@ -137,8 +137,8 @@ int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t 
  * are NaN, dispatchable is -1, and n_queued counts tokens with repetition.
  * FB_EINVAL: out == NULL, n_edges outside [0, FB_PS_MAX_EDGES], and on heartbeat contexts edges
  * not finite and strictly ascending or a non-finite now or tte.  FB_ESTATE: a sharded context
- * (its pool is the group's, which needs a collective), and out of order.  A
- * refused call changes nothing.
+ * (its pool is the group's, which needs a collective: fb_pool_stats_shard on every rank, then
+ * fb_pool_merge), and out of order.  A refused call changes nothing.
  * Replaces nothing in the reference, which keeps no such view: its only look at the pool is
  * the per-worker is_alive walk of purge_workers (task_dispatcher.py:241-249). */
 #define FB_PS_FREE_BINS 33
@@ -164,6 +164,26 @@ typedef struct fb_pool_summary {
 } fb_pool_summary;
 int fb_pool_stats(fb_ctx *ctx, double now, double tte, const double *age_edges, int32_t n_edges,
                   fb_pool_summary *out);
+
+/* Sharded contexts, between ticks: this rank's part of the group's pool summary, by the same
+ * three launches over its own slots, its log shard and the replicated queue.  In *part:
+ * n_slots is the rank's slot count; n_registered, n_expired, free_total, oldest_hb, newest_hb
+ * and both histograms cover its own slots; n_queued, n_queued_expired and dispatchable cover
+ * the queue positions whose slot is one of its own; inflight and inflight_expired cover its
+ * log shard; log_head is the global head; inflight_max is -1 (sharded contexts keep no
+ * per-slot counts).  *queue_len is the replicated queue's length.  Arguments are checked as
+ * by fb_pool_stats (and queue_len != NULL); the order rules are fb_pool_stats' (DESIGN.md
+ * §5f).  FB_ESTATE also: a one-GPU context (use fb_pool_stats). */
+int fb_pool_stats_shard(fb_ctx *ctx, double now, double tte, const double *age_edges, int32_t n_edges,
+                        fb_pool_summary *part, int64_t *queue_len);
+/* Host only, no device work, reads no lifecycle: fold the ranks' parts into the group's
+ * summary.  Integer fields and histograms are summed; oldest_hb / newest_hb are the minimum /
+ * maximum over the parts that have one (NaN when none has); inflight_max is -1 if any part's
+ * is, else the maximum; log_head is the parts' common value.  FB_EINVAL: n_parts < 1, a null
+ * pointer, parts that disagree on log_head or on their queue length, or whose queue positions
+ * do not sum to it.  ctx may be NULL (then only the code is returned). */
+int fb_pool_merge(fb_ctx *ctx, const fb_pool_summary *parts, const int64_t *queue_lens,
+                  int32_t n_parts, fb_pool_summary *out);
 
 /* Enqueue one tick on the context's stream (no host sync).
  * Replaces, per tick: the inbound branches (task_dispatcher.py:343-387), the

@@ -14,6 +14,17 @@ bytes per role are computed from the shapes (the layout of csrc/faasbal_layout.h
 counted at the bytes they use, not the sectors they move) and divided by the kernel times.
 
     python tools/stats_probe.py --out profiles/stats_probe.json
+
+``--world N``: the same cases on a shard group -- a LocalShardGroup of N rank contexts on this
+one GPU, whose ranks run one after another (a real group's run side by side, one per GPU,
+followed by one small gather).  Per repetition it times every rank's
+ShardedBalancer.pool_stats_part (fb_pool_stats_shard: wall time of the call and its kernels'
+device times) and the merge of the parts; the host leg is the group's read_state(with_log=True)
+plus the model on a twin group.  Reported: the median over repetitions of a rank's call, of
+the slowest rank's call (what a parallel group waits for), of the ranks' calls in sequence
+plus the merge (what this one-GPU group takes), and of the host leg.
+
+    python tools/stats_probe.py --world 2 --out profiles/stats_probe_shard_w2.json
 """
 import argparse
 import json
@@ -127,13 +138,95 @@ def run_case(name, head, live, W, reps):
                 role_bytes=by, kernels=rows, summary=summary)
 
 
+def run_case_shard(name, head, live, W, reps, world):
+    import torch  # noqa: F401  (loads the HIP runtime before the library)
+    from faasbal.poolstats import merge_summaries
+    from faasbal.sharded import LocalShardGroup
+
+    st = make_state(head, live, W)
+    # (a rank's log shard holds the live entries on its slots: at most `live`)
+    grp, twin = (LocalShardGroup(world, W, live + 64, max_events=64) for _ in range(2))
+    for g in (grp, twin):
+        g.load(st)
+        for b in g.bals:
+            b.sync()
+            b.read_state(with_log=False)
+            b.selftest()
+    for b in grp.bals:
+        b.timing_enable(True)
+        b.timing_read()
+    legs = {"rank_call": [], "slowest_rank_call": [], "merge": [], "device_sequential": [], "host": [], "host_read_only": []}
+    kern, got = {}, {}
+    for rep in range(reps + 1):
+        for leg in ("device", "host"):
+            if leg == "device":
+                t0 = time.perf_counter()
+                calls, parts = [], []
+                for b in grp.bals:
+                    t1 = time.perf_counter()
+                    parts.append(b.pool_stats_part(NOW, TTE, EDGES))
+                    calls.append(time.perf_counter() - t1)
+                t2 = time.perf_counter()
+                s = merge_summaries([p for p, _ in parts], [q for _, q in parts])
+                t3 = time.perf_counter()
+                times = [b.timing_read() for b in grp.bals]
+            else:
+                t0 = time.perf_counter()
+                state = twin.read_state(with_log=True)
+                t1 = time.perf_counter()
+                s = pool_stats_model(state, NOW, TTE, EDGES, inflight_counts=False)
+                t3 = time.perf_counter()
+                state = None
+            if rep == 0:  # warm-up; the summaries compared once
+                got[leg] = s
+                continue
+            if leg == "device":
+                legs["rank_call"].extend(c * 1e3 for c in calls)
+                legs["slowest_rank_call"].append(max(calls) * 1e3)
+                legs["merge"].append((t3 - t2) * 1e3)
+                legs["device_sequential"].append((t3 - t0) * 1e3)
+                for tr in times:
+                    for k, (ms, n) in tr.items():
+                        if k.startswith("ps_"):
+                            kern.setdefault(k, []).append(ms)
+            else:
+                legs["host"].append((t3 - t0) * 1e3)
+                legs["host_read_only"].append((t1 - t0) * 1e3)
+    d = diff_summary(got["device"], got["host"])
+    if d:
+        raise SystemExit("%s, world %d: the group's summary and the host's differ: %r" % (name, world, d))
+    shard_logs = [int(b.read_state(with_log=False)["log_len"]) for b in grp.bals]
+    grp.close()
+    twin.close()
+    summary = {k: (v.tolist() if isinstance(v, np.ndarray) else None if isinstance(v, float) and v != v else v)
+               for k, v in got["device"].items()}
+    return dict(head=head, live=live, W=W, Q=len(st["queue"]), reps=reps, world=world, shard_log_entries=shard_logs,
+                wall_ms={k: dict(median=med(v), min=float(min(v)), max=float(max(v))) for k, v in legs.items()},
+                speedup_slowest_rank_vs_host=med(legs["host"]) / med(legs["slowest_rank_call"]),
+                speedup_sequential_vs_host=med(legs["host"]) / med(legs["device_sequential"]),
+                kernels_per_rank_ms={k: med(v) for k, v in kern.items()},
+                record_bytes_per_rank=8 * 65, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="configs2_like,configs3_like")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--world", type=int, default=0, help="N > 0: a shard group of N ranks on this GPU")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = {"hbm_peak_bytes_per_s": HBM_PEAK, "now": NOW, "tte": TTE, "age_edges": list(EDGES), "cases": {}}
+    if a.world > 0:
+        res["world"] = a.world
+        for name in a.cases.split(","):
+            c = res["cases"][name] = run_case_shard(name, reps=a.reps, world=a.world, **CASES[name])
+            print(name, "world", a.world, json.dumps(c["wall_ms"]), json.dumps(c["kernels_per_rank_ms"]), flush=True)
+        txt = json.dumps(res, indent=1)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        print(json.dumps(res))
+        return
     for name in a.cases.split(","):
         res["cases"][name] = run_case(name, reps=a.reps, **CASES[name])
         print(name, json.dumps(res["cases"][name]["wall_ms"]), "x%.1f" % res["cases"][name]["speedup_device_vs_host"],
