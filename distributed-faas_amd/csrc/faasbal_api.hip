@@ -290,6 +290,10 @@ struct fb_ctx {
     uint32_t *xs_tk = nullptr;                        // k_xscan's ticket
     void *lc_mem = nullptr;                           // fb_log_compact's scratch (lc_plan's regions; made on first use)
     size_t lc_cap = 0;
+    // fb_log_compact_shard_mark's notes for its apply (life.marked): the exchange bitmap, the
+    // log it was made of and the rank's live count (the scratch's local regions hold the rest)
+    void *lcs_buf = nullptr;
+    int64_t lcs_head = 0, lcs_head_local = 0, lcs_live = 0;
     void *ps_mem = nullptr;                           // fb_pool_stats' scratch (ps_plan's regions; made on first use)
     size_t ps_cap = 0;
     int64_t *ps_out = nullptr, *ps_out_dev = nullptr; // ... and its folded record, host-mapped (kPsCols words)
@@ -1820,6 +1824,187 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     c->head = (int64_t)live;
     life_replaced(c->life);  // (with it the discarded FB_ENOSPC tick)
     if (n_kept) *n_kept = (int64_t)live;
+    return FB_OK;
+}
+
+// A shard group's compaction, this rank's two halves.  The scratch is
+// fb_log_compact's allocation; `keep` bytes of it (a mark's local regions) survive a growth.
+static int lcs_scratch(fb_ctx *c, const LcsPlan &p, size_t keep) {
+    if (p.bytes <= c->lc_cap) return FB_OK;
+    // sized for this log, doubling, never beyond a full one
+    const size_t full = lcs_plan(std::max<int64_t>(c->head, (int64_t)c->log_cap * c->world), c->log_cap, c->W_cap, true).bytes;
+    const size_t want = std::max(p.bytes, std::min(2 * c->lc_cap, full));
+    HIPCHK(c, stream_wait(c));
+    void *m = nullptr;
+    const hipError_t e = hipMalloc(&m, want);
+    if (e != hipSuccess)
+        return fail(c, FB_ENOMEM, "hipMalloc(compaction scratch %zu B) failed: %s", want, hipGetErrorString(e));
+    if (c->lc_mem) {
+        if (keep) {
+            const hipError_t ce = hipMemcpy(m, c->lc_mem, keep, hipMemcpyDeviceToDevice);
+            if (ce != hipSuccess) {
+                hipFree(m);
+                return fail(c, FB_EHIP, "hipMemcpy(compaction scratch) failed: %s", hipGetErrorString(ce));
+            }
+        }
+        hipFree(c->lc_mem);
+    }
+    c->lc_mem = m;
+    c->lc_cap = want;
+    return FB_OK;
+}
+
+static LcsArgs lcs_args(fb_ctx *c, const LcsPlan &p, bool want_kept) {
+    char *const base = (char *)c->lc_mem;
+    LcsArgs a{};
+    a.log = c->log_slot;
+    a.lseq = c->lseq;
+    a.head = c->head;
+    a.head_local = c->head_local;
+    a.W = c->W;
+    a.ntl = p.ntl;
+    a.ntg = p.ntg;
+    // (no sharded context commits lazily today: the test is kept for the day one does)
+    a.live_chk = c->life.stale ? 1 : 0;
+    a.slot_base = c->slot_base;
+    a.want_kept = want_kept ? 1 : 0;
+    a.reg = c->reg;
+    a.epoch = c->epoch;
+    a.lbitmap = (unsigned long long *)(base + p.lbitmap);
+    a.lwrel = (uint32_t *)(base + p.lwrel);
+    a.ltcnt = (uint32_t *)(base + p.ltcnt);
+    a.ltpre = (uint32_t *)(base + p.ltpre);
+    a.xbits = (unsigned long long *)c->lcs_buf;
+    a.gwrel = (uint32_t *)(base + p.gwrel);
+    a.gtcnt = (uint32_t *)(base + p.gtcnt);
+    a.gtpre = (uint32_t *)(base + p.gtpre);
+    a.dst = (int32_t *)(base + p.dst);
+    a.dseq = (uint32_t *)(base + p.dseq);
+    a.kept = want_kept ? (int64_t *)(base + p.kept) : nullptr;
+    return a;
+}
+// k_lc_scan over a tile count array of the shard's scratch
+static LcArgs lcs_scan_args(int nt, uint32_t *tcnt, uint32_t *tpre) {
+    LcArgs s{};
+    s.nt = nt;
+    s.tcnt = tcnt;
+    s.tpre = tpre;
+    return s;
+}
+
+int fb_log_compact_shard_bytes(fb_ctx *c, int64_t *bytes) {
+    if (!c || !bytes) return FB_EINVAL;
+    if (!c->shard) return fail(c, FB_ESTATE, "fb_log_compact_shard_bytes on a one-GPU context: use fb_log_compact");
+    // (the committed head: a mark's, while one stands)
+    *bytes = lcs_plan(c->head, 0, 0, false).xbytes;
+    return FB_OK;
+}
+
+int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int64_t *n_live_local) {
+    if (!c) return FB_EINVAL;
+    // (the refusals before the gate's duties: a refused call changes nothing, a flush aside)
+    if (c->shard && !c->life.marked) {
+        const int64_t need = lcs_plan(c->head, 0, 0, false).xbytes;
+        if (bytes < need || (need && !device_buffer) || ((uintptr_t)device_buffer & 7))
+            return fail(c, FB_EINVAL, "exchange bitmap: %lld bytes at %p, the log needs %lld, 8-byte aligned", (long long)bytes,
+                        device_buffer, (long long)need);
+    }
+    const Gate g = life_gate_log_compact_shard_mark(c->life, c->caps);
+    if (int rc_ = enter(c, g)) return rc_;  // (an uncommitted tick's clears are taken back here)
+    HIPCHK(c, hipSetDevice(c->device));
+    const LcsPlan p = lcs_plan(c->head, c->head_local, c->W, false);
+    if (int rc_ = lcs_scratch(c, p, 0)) return rc_;
+    c->lcs_buf = device_buffer;
+    const LcsArgs a = lcs_args(c, p, false);
+    if (p.flag_grid > 0) {
+        Timer t(c, "lcs_flag");
+        launch_lcs_flag(a, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(lcs_scan_args(p.ntl, a.ltcnt, a.ltpre), t.st());
+    }
+    if (p.mark_grid > 0) {
+        Timer t(c, "lcs_mark");
+        launch_lcs_mark(a, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t live = 0;
+    HIPCHK(c, hipMemcpy(&live, a.ltpre + p.ntl, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)live > c->head_local)
+        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (the log shard's entries)", live,
+                    (long long)c->head_local);
+    c->lcs_head = c->head;
+    c->lcs_head_local = c->head_local;
+    c->lcs_live = (int64_t)live;
+    life_lcs_marked(c->life);  // (with it the tick that was never committed)
+    if (n_live_local) *n_live_local = (int64_t)live;
+    return FB_OK;
+}
+
+int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_seq, int64_t cap, int64_t *n_kept_local) {
+    if (!c) return FB_EINVAL;
+    if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
+    if (int rc_ = enter(c, life_gate_log_compact_shard_apply(c->life, c->caps))) return rc_;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->head != c->lcs_head || c->head_local != c->lcs_head_local) {  // (the gates keep the log as the mark saw it)
+        life_lcs_unmarked(c->life);
+        return fail(c, FB_ESTATE, "the log changed under a marked compaction");
+    }
+    const bool want_kept = kept_seq != nullptr;
+    const LcsPlan p = lcs_plan(c->head, c->head_local, c->W, want_kept);
+    if (int rc_ = lcs_scratch(c, p, p.keep)) return rc_;
+    const LcsArgs a = lcs_args(c, p, want_kept);
+    if (p.count_grid > 0) {
+        Timer t(c, "lcs_count");
+        launch_lcs_count(a, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(lcs_scan_args(p.ntg, a.gtcnt, a.gtpre), t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t total = 0;
+    HIPCHK(c, hipMemcpy(&total, a.gtpre + p.ntg, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)total != n_live_global || n_live_global > c->head || n_live_global < c->lcs_live) {
+        life_lcs_unmarked(c->life);
+        return fail(c, FB_ESTATE, "the reduced bitmap holds %u live entries, the group agreed on %lld (this rank: %lld of %lld)",
+                    total, (long long)n_live_global, (long long)c->lcs_live, (long long)c->head);
+    }
+    if (kept_seq && cap < n_live_global)  // (the mark stays: the caller may apply again)
+        return fail(c, FB_EINVAL, "kept_seq holds %lld entries, the group's log %lld live ones", (long long)cap,
+                    (long long)n_live_global);
+    const int64_t live = c->lcs_live;
+    if (p.move.grid() > 0) {
+        Timer t(c, "lcs_move");
+        launch_lcs_move(a, t.st());
+    }
+    if (live) {
+        Timer t(c, "lc_copy");
+        launch_copy_words((uint32_t *)c->log_slot, (const uint32_t *)a.dst, live, t.st());
+    }
+    if (live) {
+        Timer t(c, "lc_copy");
+        launch_copy_words(c->lseq, a.dseq, live, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    if (kept_seq && n_live_global)
+        HIPCHK(c, hipMemcpy(kept_seq, a.kept, (size_t)n_live_global * 8, hipMemcpyDeviceToHost));
+    c->head = n_live_global;
+    c->head_local = live;
+    c->lcs_buf = nullptr;
+    life_replaced(c->life);
+    if (n_kept_local) *n_kept_local = live;
+    return FB_OK;
+}
+
+int fb_log_compact_shard_cancel(fb_ctx *c) {
+    if (!c) return FB_EINVAL;
+    c->lcs_buf = nullptr;
+    life_lcs_unmarked(c->life);
     return FB_OK;
 }
 

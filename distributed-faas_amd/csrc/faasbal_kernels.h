@@ -587,6 +587,29 @@ struct LcArgs {
 void launch_lc_flag(const LcArgs &a, Stream st);
 void launch_lc_scan(const LcArgs &a, Stream st);
 void launch_lc_move(const LcArgs &a, Stream st);
+// fb_log_compact_shard_mark / _apply (grids and the scratch regions: lcs_plan,
+// faasbal_layout.h).  Local entry i (sequence lseq[i], ascending) is live by LcArgs' rule with
+// the shard's forms: the entry names a global slot (slot_base is taken off) and the epoch test
+// compares its sequence, not its index.
+struct LcsArgs {
+    const int32_t *log;          // [head_local] the shard's entries
+    const uint32_t *lseq;        // [head_local] their global sequences
+    int64_t head, head_local;
+    int W, ntl, ntg, live_chk, slot_base, want_kept;
+    const uint8_t *reg;
+    uint32_t *epoch;             // read by the flag pass (live_chk), remapped by the move pass
+    unsigned long long *lbitmap; // [ntl * kLcWords] live bits by shard index
+    uint32_t *lwrel, *ltcnt, *ltpre;  // as LcArgs' wrel / tcnt / tpre, over the shard
+    unsigned long long *xbits;   // [ntg * kLcWords] the exchange bitmap by sequence (the caller's buffer)
+    uint32_t *gwrel, *gtcnt, *gtpre;  // ... over the reduced exchange bitmap
+    int32_t *dst;                // [live local] the shard's survivors' slots in order
+    uint32_t *dseq;              // [live local] their new sequences
+    int64_t *kept;               // [live global] old sequence of each new one (want_kept)
+};
+void launch_lcs_flag(const LcsArgs &a, Stream st);
+void launch_lcs_mark(const LcsArgs &a, Stream st);
+void launch_lcs_count(const LcsArgs &a, Stream st);
+void launch_lcs_move(const LcsArgs &a, Stream st);
 // fb_pool_stats (grids, the partial rows' columns and the scratch regions: ps_plan,
 // faasbal_layout.h).  A slot is expired iff it holds a record and (now - hb) > tte (hb_chk:
 // heartbeat contexts; the tick's test); a log entry is live by LcArgs' rule.

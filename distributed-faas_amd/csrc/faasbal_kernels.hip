@@ -5187,6 +5187,226 @@ __global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
     }
 }
 
+// ------------------------------------------------------------ a shard group's log compaction
+// fb_log_compact_shard_mark / _apply (layout: lcs_plan, faasbal_layout.h).
+//
+// k_lcs_flag: k_lc_flag over the rank's shard.  Entry i of the shard names a global slot
+// (slot_base off; the gathers at the clamped local slot, masked afterwards) and carries its
+// sequence in lseq[i], which is what the epoch test compares.
+__global__ __launch_bounds__(kBS) void k_lcs_flag(LcsArgs a) {
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.ntl) return;  // (the whole wave)
+    const int lane = lane_id();
+    const int wlast = a.W > 0 ? a.W - 1 : 0;
+    const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine = 0;  // lane j < kLcWords: word j of the tile
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch];
+        bool live[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            s[k] = a.log[i < a.head_local ? i : a.head_local - 1];
+        }
+        if (a.live_chk) {
+            uint8_t r[kLcBatch];
+            uint32_t e[kLcBatch], q[kLcBatch];
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+                const int32_t ls = s[k] - a.slot_base;
+                const int32_t sc = ls < 0 ? 0 : (ls > wlast ? wlast : ls);
+                r[k] = a.reg[sc];
+                e[k] = a.epoch[sc];
+                q[k] = a.lseq[i < a.head_local ? i : a.head_local - 1];
+            }
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) {
+                const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+                const int32_t ls = s[k] - a.slot_base;
+                live[k] = i < a.head_local && s[k] >= 0 && ls >= 0 && ls < a.W && r[k] && q[k] >= e[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) live[k] = i0 + (int64_t)(j0 + k) * 64 < a.head_local && s[k] >= 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const unsigned long long m = __ballot(live[k]);
+            if (lane == j0 + k) mine = m;
+        }
+    }
+    const uint32_t cnt = (uint32_t)__popcll(mine);
+    const uint32_t inc = wave_incl_scan_u32(cnt);
+    if (lane < kLcWords) {
+        a.lbitmap[(int64_t)tile * kLcWords + lane] = mine;
+        a.lwrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
+    }
+    if (lane == 63) a.ltcnt[tile] = inc;
+}
+
+// The rank's bits of the exchange bitmap, owner computes: a thread per word of 64 sequences.
+// The shard's sequences ascend, so the entries of a word are contiguous in the shard: a lower
+// bound into lseq finds the first, and at most 64 follow.  Every word is written (0 where the
+// rank has no live entry, past the head included): no zero pass, no atomics, and the same
+// bytes every time.
+__global__ __launch_bounds__(kBS) void k_lcs_mark(LcsArgs a) {
+    const int64_t w = (int64_t)blockIdx.x * kBS + threadIdx.x;
+    if (w >= (int64_t)a.ntg * kLcWords) return;
+    const int64_t q0 = w * 64, q1 = q0 + 64;
+    int64_t lo = 0, hi = a.head_local;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)a.lseq[mid] < q0) lo = mid + 1;
+        else hi = mid;
+    }
+    unsigned long long bits = 0;
+    if (lo < a.head_local) {
+        // the live bits of shard indices [lo, lo + 64): two words of the local bitmap
+        // (ntl * kLcWords of them: lo < head_local is inside, the next may not be)
+        const int64_t lw = lo >> 6, nwl = (int64_t)a.ntl * kLcWords;
+        const int sh = (int)(lo & 63);
+        const unsigned long long b0 = a.lbitmap[lw], b1 = lw + 1 < nwl ? a.lbitmap[lw + 1] : 0ull;
+        const unsigned long long lv = sh ? (b0 >> sh) | (b1 << (64 - sh)) : b0;
+#pragma unroll 4
+        for (int k = 0; k < 64; ++k) {
+            const int64_t i = lo + k;
+            if (i >= a.head_local) break;
+            const int64_t q = (int64_t)a.lseq[i];
+            if (q >= q1 || q >= a.head) break;
+            if ((lv >> k) & 1ull) bits |= 1ull << (q - q0);
+        }
+    }
+    a.xbits[w] = bits;
+}
+
+#ifdef FB_LCS_MARK_ATOMIC
+// The other form of the mark, measured against k_lcs_mark and not kept as the default
+// (a diagnostic build: build_lib(defines=("FB_LCS_MARK_ATOMIC",))): a zero pass
+// over the exchange bitmap, then a wave per local tile ORs its live entries' bits in, the lanes
+// that hit one word combined first (one vector atomic per word and wave step).
+__global__ __launch_bounds__(kBS) void k_lcs_zero(LcsArgs a) {
+    const int64_t w = (int64_t)blockIdx.x * kBS + threadIdx.x;
+    if (w < (int64_t)a.ntg * kLcWords) a.xbits[w] = 0ull;
+}
+__global__ __launch_bounds__(kBS) void k_lcs_mark_atomic(LcsArgs a) {
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.ntl) return;  // (the whole wave)
+    const int lane = lane_id();
+    const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    const unsigned long long mine = lane < kLcWords ? a.lbitmap[(int64_t)tile * kLcWords + lane] : 0ull;
+    for (int j = 0; j < kLcWords; ++j) {
+        const unsigned long long m = __shfl(mine, j, 64);
+        if (!m) continue;  // (wave-uniform)
+        const int64_t i = i0 + (int64_t)j * 64;
+        const uint32_t q = a.lseq[i < a.head_local ? i : a.head_local - 1];
+        bool todo = ((m >> lane) & 1ull) && (int64_t)q < a.head;
+        const uint32_t w = q >> 6;
+        const unsigned long long bit = 1ull << (q & 63);
+        unsigned long long left = __ballot(todo);
+        while (left) {
+            const int lead = __ffsll((long long)left) - 1;
+            const uint32_t lw = (uint32_t)__shfl((int)w, lead, 64);
+            const bool same = todo && w == lw;
+            unsigned long long v = same ? bit : 0ull;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+            if (lane == lead) atomicOr(&a.xbits[lw], v);
+            todo = todo && !same;
+            left = __ballot(todo);
+        }
+    }
+}
+#endif
+
+// The reduced exchange bitmap counted: each word's set bits before it in its tile (gwrel), each
+// tile's (gtcnt) -- k_lc_flag's last step, the bitmap given.
+__global__ __launch_bounds__(kBS) void k_lcs_count(LcsArgs a) {
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.ntg) return;  // (the whole wave)
+    const int lane = lane_id();
+    const unsigned long long mine = lane < kLcWords ? a.xbits[(int64_t)tile * kLcWords + lane] : 0ull;
+    const uint32_t cnt = (uint32_t)__popcll(mine);
+    const uint32_t inc = wave_incl_scan_u32(cnt);
+    if (lane < kLcWords) a.gwrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
+    if (lane == 63) a.gtcnt[tile] = inc;
+}
+
+// set bits of the reduced bitmap below sequence q, q <= head (the rank query of k_lc_move)
+__device__ __forceinline__ uint32_t lcs_rank(const LcsArgs &a, uint64_t q) {
+    if (q >= (uint64_t)a.head) return a.gtpre[a.ntg];
+    const int64_t w = (int64_t)(q >> 6);
+    return a.gtpre[q / kLcTile] + a.gwrel[w] + (uint32_t)__popcll(a.xbits[w] & ((1ull << (q & 63)) - 1ull));
+}
+
+// Local tile workgroups: survivor i of the shard goes to ltpre[tile] + lwrel[word] + its rank in
+// the word, with the rank of its sequence in the reduced bitmap as its new sequence (out of
+// place: the apply copies dst and dseq back).  Slot workgroups: epoch[s] = that rank of
+// min(epoch[s], head).  Kept workgroups (want_kept): k_lc_move's kept scatter over the reduced
+// bitmap -- set bit q goes to kept[its rank].
+__global__ __launch_bounds__(kBS) void k_lcs_move(LcsArgs a) {
+    const LcsMoveLayout lay = lcs_move_layout(a.ntl, a.W, a.want_kept ? a.ntg : 0);
+    const int bid = (int)blockIdx.x;
+    const int lane = lane_id();
+    if (bid >= lay.end(kLcsMoveSlots)) {
+        const int tile = lay.rel(kLcsMoveKept, bid) * kWaves + wave_id();
+        if (tile >= a.ntg) return;  // (the whole wave)
+        unsigned long long mine = 0;
+        uint32_t pre = 0;
+        if (lane < kLcWords) {
+            mine = a.xbits[(int64_t)tile * kLcWords + lane];
+            pre = a.gtpre[tile] + a.gwrel[(int64_t)tile * kLcWords + lane];
+        }
+#pragma unroll 4
+        for (int j = 0; j < kLcWords; ++j) {
+            const unsigned long long m = __shfl(mine, j, 64);
+            const uint32_t p = (uint32_t)__shfl((int)pre, j, 64);
+            // (the count was checked against the caller's total <= head: the index is inside)
+            if ((m >> lane) & 1ull) a.kept[(int64_t)p + popc_lt(m)] = (int64_t)tile * kLcTile + j * 64 + lane;
+        }
+        return;
+    }
+    if (bid >= lay.end(kLcsMoveTiles)) {
+        const int s = lay.rel(kLcsMoveSlots, bid) * kBS + (int)threadIdx.x;
+        if (s >= a.W) return;
+        a.epoch[s] = lcs_rank(a, a.epoch[s]);
+        return;
+    }
+    const int tile = bid * kWaves + wave_id();
+    if (tile >= a.ntl) return;  // (the whole wave)
+    const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine = 0;
+    uint32_t pre = 0;
+    if (lane < kLcWords) {
+        mine = a.lbitmap[(int64_t)tile * kLcWords + lane];
+        pre = a.ltpre[tile] + a.lwrel[(int64_t)tile * kLcWords + lane];
+    }
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch];
+        uint32_t q[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            const int64_t ic = i < a.head_local ? i : a.head_local - 1;
+            s[k] = a.log[ic];
+            q[k] = a.lseq[ic];
+        }
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const unsigned long long m = __shfl(mine, j0 + k, 64);
+            const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
+            if ((m >> lane) & 1ull) {  // (a set bit: i < head_local)
+                const int64_t o = (int64_t)p + popc_lt(m);
+                // (a sequence is below the head: fb_load_shard and the ticks see to it; clamped
+                // so that a broken one cannot send the query outside the scratch)
+                const uint64_t qc = (uint64_t)q[k] < (uint64_t)a.head ? q[k] : (uint64_t)a.head - 1;
+                a.dst[o] = s[k];
+                a.dseq[o] = lcs_rank(a, qc);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------ pool summary
 // fb_pool_stats (layout: ps_plan, faasbal_layout.h): reductions and two small histograms over
 // the committed arrays, read only.  Every load is unconditional at a clamped index and masked
@@ -5598,6 +5818,30 @@ void launch_lc_scan(const LcArgs &a, Stream st) {
 void launch_lc_move(const LcArgs &a, Stream st) {
     const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
     if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lc_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_lcs_flag(const LcsArgs &a, Stream st) {
+    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
+    if (p.flag_grid > 0) hipExtLaunchKernelGGL(k_lcs_flag, dim3(p.flag_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_lcs_mark(const LcsArgs &a, Stream st) {
+    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
+#ifdef FB_LCS_MARK_ATOMIC
+    if (p.mark_grid > 0) {
+        hipExtLaunchKernelGGL(k_lcs_zero, dim3(p.mark_grid), dim3(kBS), 0, st.s, st.e0, p.flag_grid > 0 ? nullptr : st.e1, 0, a);
+        if (p.flag_grid > 0)
+            hipExtLaunchKernelGGL(k_lcs_mark_atomic, dim3(p.flag_grid), dim3(kBS), 0, st.s, nullptr, st.e1, 0, a);
+    }
+#else
+    if (p.mark_grid > 0) hipExtLaunchKernelGGL(k_lcs_mark, dim3(p.mark_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+#endif
+}
+void launch_lcs_count(const LcsArgs &a, Stream st) {
+    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
+    if (p.count_grid > 0) hipExtLaunchKernelGGL(k_lcs_count, dim3(p.count_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+}
+void launch_lcs_move(const LcsArgs &a, Stream st) {
+    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
+    if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lcs_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
 void launch_ps_slots(const PsArgs &a, Stream st) {
     const PsPlan p = ps_plan(a.W, a.Qn, a.head);

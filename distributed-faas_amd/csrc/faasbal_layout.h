@@ -305,6 +305,72 @@ inline LcPlan lc_plan(int64_t head, int W, bool want_kept) {
 }
 
 // ---------------------------------------------------------------------------------------
+// fb_log_compact_shard_mark / _apply: a rank's two halves of its group's compaction.  The
+// shard holds head_local entries (lseq: their global sequences, ascending) of the `head`
+// sequences; local tiles and words are over the shard's indices, global ones over sequences.
+//   mark:   k_lcs_flag   a workgroup per four local tiles: k_lc_flag's three outputs over the
+//                        shard (lbitmap, lwrel, ltcnt)
+//           k_lc_scan    ltpre over the local tiles; ltpre[ntl] = the rank's live count
+//           k_lcs_mark   a thread per global word: the rank's bits of the exchange bitmap
+//                        (the caller's buffer, nwg words, every one written)
+//   apply:  k_lcs_count  a workgroup per four global tiles of the reduced bitmap: gwrel, gtcnt
+//           k_lc_scan    gtpre; gtpre[ntg] = the group's live count
+//           k_lcs_move   the local tile workgroups scatter the shard's survivors (dst: slots,
+//                        dseq: new sequences), a workgroup per kBS slots remaps the epochs,
+//                        then (want_kept) the global tile workgroups expand the bitmap (kept)
+// The local regions come first: they are written by the mark and read by the apply, and stay
+// where they are (or are copied, `keep` bytes) when the apply grows the scratch for a kept list.
+enum { kLcsMoveTiles, kLcsMoveSlots, kLcsMoveKept };
+struct LcsMoveLayout : Roles<3> {};
+FB_HD LcsMoveLayout lcs_move_layout(int ntl, int W, int ntg_kept) {
+    return {{{quarter(ntl), (int)cdiv(W, kBS), quarter(ntg_kept)}}};
+}
+struct LcsPlan {
+    int ntl, ntg;      // local tiles (of shard indices), global tiles (of sequences)
+    int64_t nwl, nwg;  // local bitmap words, global (exchange) bitmap words
+    int flag_grid, mark_grid, count_grid, scan_grid;
+    LcsMoveLayout move;
+    // regions: nwl x 8, nwl x 4, ntl x 4, (ntl + 1) x 4 | nwg x 4, ntg x 4, (ntg + 1) x 4,
+    // head_local x 4, head_local x 4, head x 8 bytes
+    size_t lbitmap, lwrel, ltcnt, ltpre, gwrel, gtcnt, gtpre, dst, dseq, kept;
+    size_t keep;       // the bytes a mark leaves for its apply: [0, keep)
+    size_t bytes;
+    int64_t xbytes;    // the exchange bitmap: nwg x 8 bytes
+};
+inline LcsPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept) {
+    LcsPlan p{};
+    p.ntl = (int)cdiv(head_local, kLcTile);
+    p.ntg = (int)cdiv(head, kLcTile);
+    p.nwl = (int64_t)p.ntl * kLcWords;
+    p.nwg = (int64_t)p.ntg * kLcWords;
+    p.flag_grid = quarter(p.ntl);
+    p.mark_grid = (int)cdiv(p.nwg, kBS);
+    p.count_grid = quarter(p.ntg);
+    p.scan_grid = 1;
+    p.move = lcs_move_layout(p.ntl, W, want_kept ? p.ntg : 0);
+    p.xbytes = p.nwg * 8;
+    size_t o = 0;
+    auto take = [&o](size_t b) {
+        const size_t at = o;
+        o += (b + 255) & ~(size_t)255;
+        return at;
+    };
+    p.lbitmap = take((size_t)p.nwl * 8);
+    p.lwrel = take((size_t)p.nwl * 4);
+    p.ltcnt = take((size_t)p.ntl * 4);
+    p.ltpre = take(((size_t)p.ntl + 1) * 4);
+    p.keep = o;
+    p.gwrel = take((size_t)p.nwg * 4);
+    p.gtcnt = take((size_t)p.ntg * 4);
+    p.gtpre = take(((size_t)p.ntg + 1) * 4);
+    p.dst = take((size_t)head_local * 4);
+    p.dseq = take((size_t)head_local * 4);
+    p.kept = take(want_kept ? (size_t)head * 8 : 0);
+    p.bytes = o;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------
 // fb_pool_stats: three launches, none of which writes anything but the scratch.
 //   k_ps_slots  slot workgroups (kPsTiles tiles of kBS slots each: the counts, sums, minima
 //               and histograms of a row of kPsCols words, and the expired bitmap, a 64-bit

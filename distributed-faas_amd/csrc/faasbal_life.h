@@ -44,6 +44,9 @@ struct Life {
     bool cm_pending = false;  // the last commit is deferred into the next launch (or a flush)
     int undo_E = 0;           // > 0: messages of a launch whose in-place clears are not committed
     bool stale = false;       // lazy clears: entries of dead registrations may be in the log
+    // sharded: fb_log_compact_shard_mark done, its apply or cancel to come (no tick meanwhile:
+    // pos is none, nothing is staged, nothing is owed)
+    bool marked = false;
 };
 
 inline bool life_launched(const Life &l) { return l.pos != Pos::none && l.pos != Pos::dropped; }
@@ -85,6 +88,8 @@ struct Gate {
     unsigned duties = 0;
 };
 
+constexpr const char *kLifeMarkedRefusal = "a log compaction is marked: apply or cancel first";
+
 inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     const bool launched = life_launched(l), waited = life_waited(l), in_flight = launched && !waited;
     // a launched window tick moves the committed window (its commit may already have run on the
@@ -95,6 +100,11 @@ inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     const unsigned undo = (l.undo_E > 0 && (l.pos == Pos::failed || l.pos == Pos::dropped)) ? kUndo : 0;
     const auto no = [](const char *m, unsigned d = 0) { return Gate{m, d}; };
     const auto ok = [](unsigned d = 0) { return Gate{nullptr, d}; };
+    // between a group compaction's mark and its apply the ranks hold a bitmap of this log: every
+    // call that reads or changes the log or launches a tick waits (fb_pool_stats_shard, whose
+    // gate ends here, too); what touches neither goes on
+    if (l.marked && call != Call::exchange_bytes && call != Call::debug_read && call != Call::sync)
+        return no(kLifeMarkedRefusal);
     switch (call) {
     case Call::load_state:  // (accepted over any tick, window ticks included; a staged batch stays)
         return k.sharded ? no("sharded context: use fb_load_shard", flush) : ok(flush);
@@ -190,6 +200,31 @@ inline Gate life_gate_pool_stats_shard(const Life &l, const CtxCaps &k) {
     return life_gate(l, one, Call::pool_stats);
 }
 
+// fb_log_compact_shard_mark, a rank's first half of its group's compaction.  Like a load it
+// discards a tick that was never committed -- waited for (another rank failed), failed or
+// dropped -- after taking its in-place clears back (kUndo; kDiscard: life_lcs_marked).  A tick
+// in flight may still write the log, staged events carry sequences of the old numbering, and an
+// eager commit (no sharded context enqueues one) would have moved the committed state already.
+inline Gate life_gate_log_compact_shard_mark(const Life &l, const CtxCaps &k) {
+    const unsigned flush = l.cm_pending ? (unsigned)kFlush : 0u;
+    if (!k.sharded) return Gate{"fb_log_compact_shard_mark on a one-GPU context: use fb_log_compact", flush};
+    if (l.marked) return Gate{kLifeMarkedRefusal, 0u};
+    if (l.staged)
+        return Gate{"fb_log_compact_shard_mark with staged events pending: their sequences would go stale", 0u};
+    if (l.pos == Pos::phase1 || l.pos == Pos::launched || (life_launched(l) && l.eager))
+        return Gate{"fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first", 0u};
+    const unsigned undo = l.undo_E > 0 ? (unsigned)kUndo : 0u, discard = life_launched(l) ? (unsigned)kDiscard : 0u;
+    return Gate{nullptr, flush | undo | discard};
+}
+// fb_log_compact_shard_apply: only after a mark (which left no tick, nothing staged, nothing owed)
+inline Gate life_gate_log_compact_shard_apply(const Life &l, const CtxCaps &k) {
+    if (!k.sharded)
+        return Gate{"fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact",
+                    l.cm_pending ? (unsigned)kFlush : 0u};
+    if (!l.marked) return Gate{"fb_log_compact_shard_apply without fb_log_compact_shard_mark", 0u};
+    return Gate{};
+}
+
 // The second gate, where a log pointer or copy is handed out: the deferred clears of the
 // entries lazy commits left, all at once (after the flush above).
 inline bool life_settle_due(const Life &l) { return l.stale; }
@@ -261,13 +296,24 @@ inline void life_undone(Life &l) {
     if (l.pos == Pos::dropped) l.pos = Pos::none;
 }
 inline void life_settled(Life &l) { l.stale = false; }
-// A successful fb_load_state / fb_load_shard / fb_log_compact: the new log holds only live
-// entries, and a launch's notes name entries of the log it replaced (or the old numbering).
+// A successful fb_load_state / fb_load_shard / fb_log_compact / fb_log_compact_shard_apply: the
+// new log holds only live entries, and a launch's notes name entries of the log it replaced (or
+// the old numbering).
 // A rejected load or compaction changes nothing.  (A staged batch stays.)
 inline void life_replaced(Life &l) {
     life_idle_(l);
     l.undo_E = 0;
     l.stale = false;
+    l.marked = false;
 }
+// fb_log_compact_shard_mark succeeded (after the gate's undo): the uncommitted tick is gone, as
+// after a load; the committed state, lazily kept entries included, is what it was
+inline void life_lcs_marked(Life &l) {
+    life_idle_(l);
+    l.undo_E = 0;
+    l.marked = true;
+}
+// fb_log_compact_shard_cancel, or an apply whose count disagreed: the mark is dropped
+inline void life_lcs_unmarked(Life &l) { l.marked = false; }
 
 }  // namespace fb

@@ -28,7 +28,9 @@ EXPORTS = ("fb_create", "fb_destroy", "fb_last_error", "fb_load_state", "fb_read
            "fb_read_inflight", "fb_set_compact", "fb_get_outputs_compact", "fb_expand_compact",
            "fb_set_window", "fb_window_stats", "fb_set_compact_out", "fb_set_eager_commit", "fb_set_path",
            "fb_set_round_hint", "fb_set_full_assign", "fb_timing_gate", "fb_timing_span",
-           "fb_timing_mark", "fb_log_compact", "fb_pool_stats", "fb_pool_stats_shard", "fb_pool_merge")
+           "fb_timing_mark", "fb_log_compact", "fb_pool_stats", "fb_pool_stats_shard", "fb_pool_merge",
+           "fb_log_compact_shard_bytes", "fb_log_compact_shard_mark", "fb_log_compact_shard_apply",
+           "fb_log_compact_shard_cancel")
 
 
 class TickResult(C.Structure):
@@ -140,6 +142,10 @@ def load(path=None):
         "fb_purge_launch": (C.c_int, [_P, dbl, dbl]),
         "fb_read_inflight": (C.c_int, [_P, _P]),
         "fb_log_compact": (C.c_int, [_P, i64, _P, i64, C.POINTER(i64)]),
+        "fb_log_compact_shard_bytes": (C.c_int, [_P, C.POINTER(i64)]),
+        "fb_log_compact_shard_mark": (C.c_int, [_P, _P, i64, C.POINTER(i64)]),
+        "fb_log_compact_shard_apply": (C.c_int, [_P, i64, _P, i64, C.POINTER(i64)]),
+        "fb_log_compact_shard_cancel": (C.c_int, [_P]),
         "fb_pool_stats": (C.c_int, [_P, dbl, dbl, _P, C.c_int32, C.POINTER(PoolSummary)]),
         "fb_pool_stats_shard": (C.c_int, [_P, dbl, dbl, _P, C.c_int32, C.POINTER(PoolSummary), C.POINTER(i64)]),
         "fb_pool_merge": (C.c_int, [_P, C.POINTER(PoolSummary), C.POINTER(i64), C.c_int32, C.POINTER(PoolSummary)]),

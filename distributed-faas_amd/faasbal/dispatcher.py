@@ -123,7 +123,7 @@ class GpuPushDispatcher:
         self.balancer.load_state(np.zeros(W, np.uint8), np.zeros(W, np.int32), np.zeros(W, np.float64))
         self.ticks = 0
         self.compactions = 0
-        self.device_compactions = 0                    # ... of which on the device (fb_log_compact)
+        self.device_compactions = 0                    # ... of which on the device (the balancer's compact_log)
         self.stats_every = 0                           # N > 0: publish_stats() after every N-th tick (0: never)
 
     @classmethod
@@ -501,9 +501,11 @@ class GpuPushDispatcher:
         """Renumber the in-flight log densely (completed and redistributed entries
         dropped); epochs are remapped so every registration keeps exactly its own
         in-flight entries.  Called only when the log would overflow.  A balancer with
-        ``compact_log`` (a one-GPU ``GpuBalancer``: fb_log_compact) renumbers on the
-        device and keeps its tick pipeline; the host only remaps its own two dicts from
-        the kept list.  Otherwise (shard groups, or a device log that disagrees with
+        ``compact_log`` (a one-GPU ``GpuBalancer``: fb_log_compact; a shard group whose
+        ranks have the parts: ``ShardGroup.compact_log``, fb_log_compact_shard_mark /
+        _apply around one all-reduce) renumbers on the device and keeps its tick
+        pipeline; the host only remaps its own two dicts from the kept list.  Otherwise
+        (a group of ranks without the parts, or a device log that disagrees with
         ``inflight``) the host path: the whole state read, renumbered and loaded again."""
         device = getattr(self.balancer, "compact_log", None)
         if callable(device):

@@ -27,6 +27,8 @@ from ._lib import FB_ERERUN, FaasbalError
 from .poolstats import HISTS, SCALARS, merge_summaries
 
 MAX_RELAUNCH = 6  # FB_ERERUN: each relaunch at least doubles the round table
+# a rank balancer's parts of a group compaction (ShardGroup.compact_log)
+COMPACT_PARTS = ("compact_mark", "compact_exchange", "compact_apply", "compact_cancel")
 
 
 def shard_range(n_workers, world, rank):
@@ -99,6 +101,51 @@ class ShardedBalancer(GpuBalancer):
         d["free_hist"] = np.array(out.free_hist, np.int64)
         d["age_hist"] = np.array(out.age_hist, np.int64)
         return d, qn.value
+
+    # ----------------------------------------------- the group's log compaction, this rank's parts
+    def compact_bytes(self):
+        """fb_log_compact_shard_bytes: the size of the live bitmap the ranks reduce (the same
+        on every rank; 0 for an empty log)."""
+        n = C.c_int64()
+        self._chk(self.lib.fb_log_compact_shard_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def compact_exchange(self, zeroed=False):
+        """The bitmap to all-reduce (SUM over uint8): a view of a torch tensor kept between
+        compactions and grown when the log needs more.  ``zeroed``: the view filled with zeros
+        (a rank whose mark failed joins the reduction with nothing)."""
+        n = self.compact_bytes()
+        buf = getattr(self, "_cbuf", None)
+        if buf is None or buf.numel() < n:
+            buf = self._cbuf = self.torch.empty(max(2 * n, 4096), dtype=self.torch.uint8, device=self.xbuf.device)
+        view = buf[:n]
+        if zeroed:
+            with self.torch.cuda.stream(self.stream):
+                view.zero_()
+        return view
+
+    def compact_mark(self):
+        """fb_log_compact_shard_mark: this rank's live bits into ``compact_exchange()``;
+        returns its live count.  An uncommitted tick is discarded."""
+        view = self.compact_exchange()
+        live = C.c_int64()
+        self._chk(self.lib.fb_log_compact_shard_mark(self.h, C.c_void_p(self._cbuf.data_ptr()), view.numel(),
+                                                     C.byref(live)))
+        return live.value
+
+    def compact_apply(self, total, want_kept=False):
+        """fb_log_compact_shard_apply after the reduction: ``total`` is the sum of the ranks'
+        live counts.  Returns dict(n_kept, n_kept_local, kept): ``kept`` the GLOBAL kept list
+        (``kept[new] = old``) with ``want_kept``, else None."""
+        n = C.c_int64()
+        kept = np.zeros(max(int(total), 1), np.int64) if want_kept else None
+        self._chk(self.lib.fb_log_compact_shard_apply(self.h, int(total), None if kept is None else
+                                                      kept.ctypes.data_as(C.c_void_p), int(total), C.byref(n)))
+        return {"n_kept": int(total), "n_kept_local": n.value, "kept": None if kept is None else kept[: int(total)]}
+
+    def compact_cancel(self):
+        """fb_log_compact_shard_cancel: drop a mark (nothing has changed)."""
+        self._chk(self.lib.fb_log_compact_shard_cancel(self.h))
 
     def load(self, st):
         """Load this rank's part of a global state dict."""
@@ -246,6 +293,9 @@ class ShardGroup:
         # test doubles: no device summary, and GpuPushDispatcher.pool_stats reads the state
         if not all(callable(getattr(b, "pool_stats_part", None)) for b in rank_balancers):
             self.pool_stats = None
+        # ... or without the parts of a compaction: GpuPushDispatcher.compact_log takes its host path
+        if not all(callable(getattr(b, m, None)) for b in rank_balancers for m in COMPACT_PARTS):
+            self.compact_log = None
 
     def _each(self, op, **kw):  # -> list of per-rank results, rank order
         raise NotImplementedError
@@ -261,6 +311,18 @@ class ShardGroup:
             raise FaasbalError(_lib.FB_ESTATE, "the ranks' parts cover %d slots, the table has %d"
                                % (out["n_slots"], self.n_workers_global))
         return out
+
+    def compact_log(self, expect=None, want_kept=True):
+        """The group's in-flight log renumbered densely where the shards live
+        (``GpuBalancer.compact_log``'s contract: dict(n_kept, kept), ``kept[new] = old``
+        global sequence, or None without ``want_kept``): every rank marks its live bits, the
+        bitmaps are all-reduced, every rank renumbers its shard against the union and remaps
+        its epochs; the dispatcher's rank reads the kept list off the bitmap.  Everything else
+        of the state and the ranks' tick pipelines stay.  ``expect``: the live count the
+        caller's mirror holds -- FB_ESTATE, every rank cancelled and every shard as it was
+        when the group's total differs, or when a rank could not mark."""
+        out = self._each("compact", expect=-1 if expect is None else int(expect), want_kept=bool(want_kept))[0]
+        return {"n_kept": out["n_kept"], "kept": out["kept"]}
 
     def load_state(self, reg, free, hb, epoch=None, queue=(), log=()):
         W = len(reg)
@@ -317,7 +379,95 @@ def serve_op(bal, op, kw, allreduce=None, commit=True):
         return bal.purge(kw["now"], kw["tte"], allreduce=allreduce, commit=commit)
     if op == "stats":  # (reads only: nothing to commit, nothing to settle)
         return bal.pool_stats_part(kw["now"], kw["tte"], kw["age_edges"])
+    if op == "compact":  # (a collective of its own: mark, reduce, agree, apply or cancel)
+        import torch.distributed as dist
+        out, bad = _compact_rank(dist, _dev(dist), bal, kw, allreduce)
+        if bad is not None:
+            _raise_bad(op, bad)
+        return out
     raise ValueError("unknown group operation %r" % op)
+
+
+def _raise_bad(op, bad):
+    code, msg = bad
+    if code is None:
+        raise RuntimeError("shard operation %r failed on a rank: %s" % (op, msg))
+    raise FaasbalError(code, "shard operation %r failed on a rank: %s" % (op, msg))
+
+
+def _failure(e):
+    return (getattr(e, "code", None), "%s: %s" % (type(e).__name__, e))
+
+
+def _compact_verdict(marks, expect):
+    """(the group's live count, the first failure or None) from every rank's guarded mark."""
+    bad = next((m[1] for m in marks if not m[0]), None)
+    total = sum(int(m[1]) for m in marks if m[0])
+    if bad is None and expect >= 0 and expect != total:
+        bad = (_lib.FB_ESTATE, "the group's log holds %d live entries, the caller expected %d" % (total, expect))
+    return total, bad
+
+
+def _compact_reduce(bal, x, allreduce):
+    """The bitmap all-reduced in place, on the rank's stream where it has one (as a tick's exchange)."""
+    import contextlib
+    stream = getattr(bal, "stream", None)
+    with (bal.torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+        if allreduce is None:
+            import torch.distributed as dist
+            dist.all_reduce(x, async_op=True).wait()
+        else:
+            allreduce(x)
+
+
+def _gather_flags(dist, dev, ok, err, word=0):
+    """One fixed header per rank, all-gathered: (ok, code, word).  Returns, on every rank, the
+    list of (ok, word | (code, message)) in rank order; messages follow pickled only when a
+    rank failed, as for ticks."""
+    import torch
+    world = dist.get_world_size()
+    h = torch.zeros(_HDR, dtype=torch.int64)
+    h[0] = 1 if ok else 0
+    h[1] = 0 if ok or err[0] is None else int(err[0])
+    h[2] = int(word)
+    hs = [torch.zeros(_HDR, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(hs, h.to(dev))
+    hs = [x.cpu().numpy() for x in hs]
+    if all(x[0] for x in hs):
+        return [(True, int(x[2])) for x in hs]
+    msgs = [None] * world
+    dist.all_gather_object(msgs, None if ok else err)
+    return [(True, int(x[2])) if x[0] else (False, msgs[i]) for i, x in enumerate(hs)]
+
+
+def _compact_rank(dist, dev, bal, kw, allreduce=None):
+    """A group compaction on this rank (every rank runs it): mark, the bitmap's all-reduce --
+    which a rank whose mark failed joins with zeros of the agreed size, so that no rank blocks
+    in the collective --, one header all-gather of the ranks' ok flags and live counts, then
+    every rank applies or every rank cancels.  Rank 0 asks for the kept list.  Returns
+    (this rank's compact_apply result or None, the first failure or None)."""
+    try:
+        mark = (True, bal.compact_mark())
+    except Exception as e:  # noqa: BLE001 -- reported to rank 0, which raises it
+        mark = (False, _failure(e))
+    x = bal.compact_exchange(zeroed=not mark[0])
+    if x.numel():
+        _compact_reduce(bal, x, allreduce)
+    marks = _gather_flags(dist, dev, mark[0], None if mark[0] else mark[1], mark[1] if mark[0] else 0)
+    total, bad = _compact_verdict(marks, kw["expect"])
+    out = None
+    if bad is None:
+        try:
+            done = (True, bal.compact_apply(total, bool(kw["want_kept"]) and dist.get_rank() == 0))
+        except Exception as e:  # noqa: BLE001
+            done = (False, _failure(e))
+        # (the count gives every rank the same verdict; what is left is a rank's own runtime error)
+        flags = _gather_flags(dist, dev, done[0], None if done[0] else done[1])
+        bad = next((f[1] for f in flags if not f[0]), None)
+        out = done[1] if done[0] else None
+    if bad is not None:
+        bal.compact_cancel()
+    return out, bad
 
 
 def _serve_guarded(bal, op, kw):
@@ -351,7 +501,11 @@ def _settle(bal, op, outs):
 # int64 record (an ok flag, a code, the queue's length, then fb_pool_summary's words in
 # the struct's order, doubles as bit patterns), all-gathered so that every rank sees every
 # flag; only when a rank failed do the messages follow, pickled, as for ticks.
-_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6}
+# A log compaction ("compact") is a header alone: the caller's expected live count (-1: none)
+# in the event count's word, whether rank 0 wants the kept list in the tasks' word.  Its
+# payload is the live bitmap, all-reduced in place like a tick's exchange; one fixed header
+# per rank (ok flag, code, live count) is all-gathered before the apply and one after it.
+_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6, "compact": 7}
 _OP_NAMES = {v: k for k, v in _OP_CODES.items()}
 _HDR = 8  # int64 words of the call header / the per-rank result header
 _PS_WORDS = C.sizeof(_lib.PoolSummary) // 8  # fb_pool_summary's words (SCALARS' order, then HISTS')
@@ -413,6 +567,9 @@ def _bcast_call(dist, dev, op, kw):
         h[1] = len(kw["age_edges"])
         h[3] = int(np.float64(kw["now"]).view(np.int64))
         h[4] = int(np.float64(kw["tte"]).view(np.int64))
+    elif op == "compact":  # (the header is the whole call)
+        h[1] = int(kw["expect"])
+        h[2] = 1 if kw["want_kept"] else 0
     dist.broadcast(h.to(dev), src=0)
     if op in ("tick", "purge"):
         if int(h[1]):
@@ -420,7 +577,7 @@ def _bcast_call(dist, dev, op, kw):
     elif op == "stats":
         if int(h[1]):
             dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["age_edges"], np.float64)).to(dev), src=0)
-    elif op != "stop":
+    elif op not in ("stop", "compact"):
         dist.broadcast_object_list([kw], src=0)
 
 
@@ -431,6 +588,8 @@ def _recv_call(dist, dev):
     dist.broadcast(h, src=0)
     h = h.cpu().numpy()
     op = _OP_NAMES[int(h[0])]
+    if op == "compact":
+        return op, dict(expect=int(h[1]), want_kept=bool(h[2]))
     if op == "stats":
         edges = torch.zeros(int(h[1]), dtype=torch.float64, device=dev)
         if int(h[1]):
@@ -555,7 +714,8 @@ class DistShardGroup(ShardGroup):
     all-reduce over the group's backend (RCCL over xGMI for ``nccl``) -- and the
     per-rank results come back to rank 0.  Ticks and purges travel as tensors (the
     event batch in one broadcast, the results in one gather) and so do pool summaries (one
-    fixed record per rank); loads and state reads as pickled objects."""
+    fixed record per rank) and log compactions (the live bitmap all-reduced in place, a fixed
+    header per rank); loads and state reads as pickled objects."""
 
     def __init__(self, balancer, n_workers):
         super().__init__(n_workers, (balancer,))
@@ -569,14 +729,16 @@ class DistShardGroup(ShardGroup):
 
     def _each(self, op, **kw):
         _bcast_call(self.dist, self.dev, op, kw)
+        if op == "compact":
+            out, bad = _compact_rank(self.dist, self.dev, self.bal, kw)
+            if bad is not None:
+                _raise_bad(op, bad)
+            return [out]
         guarded = _serve_guarded(self.bal, op, kw)
         outs = _gather(self.dist, self.dev, op, guarded)
         bad = _settle(self.bal, op, outs)
         if bad is not None:
-            code, msg = bad
-            if code is None:
-                raise RuntimeError("shard operation %r failed on a rank: %s" % (op, msg))
-            raise FaasbalError(code, "shard operation %r failed on a rank: %s" % (op, msg))
+            _raise_bad(op, bad)
         return [o[1] for o in outs]
 
     def close(self):
@@ -591,6 +753,9 @@ def serve_shard(balancer):
         op, kw = _recv_call(dist, dev)
         if op == "stop":
             return
+        if op == "compact":
+            _compact_rank(dist, dev, balancer, kw)  # rank 0 raises a failure; this rank keeps serving
+            continue
         guarded = _serve_guarded(balancer, op, kw)
         outs = _gather(dist, dev, op, guarded)
         _settle(balancer, op, outs)  # rank 0 raises a failure; this rank keeps serving
@@ -609,7 +774,40 @@ class LocalShardGroup(ShardGroup):
     def _each(self, op, **kw):
         if op in ("tick", "purge"):
             return self._collective(op, kw)
+        if op == "compact":
+            return self._compact(kw)
         return [serve_op(b, op, kw) for b in self.bals]
+
+    def _compact(self, kw):
+        # mark on every rank, the bitmaps summed on the device (as _collective_once sums the
+        # exchange), apply on every rank -- or, when a rank could not mark or the total is not
+        # the caller's, cancel on every rank: nothing has changed anywhere
+        def guarded(f, *a):
+            try:
+                return (True, f(*a))
+            except Exception as e:  # noqa: BLE001 -- raised below, once every rank is cancelled
+                return (False, _failure(e))
+
+        total, bad = _compact_verdict([guarded(b.compact_mark) for b in self.bals], kw["expect"])
+        outs = []
+        if bad is None:
+            xs = [b.compact_exchange() for b in self.bals]
+            if xs[0].numel():
+                sync = self.bals[0].torch.cuda.synchronize if xs[0].is_cuda else (lambda: None)
+                sync()
+                union = xs[0].clone()
+                for x in xs[1:]:
+                    union += x
+                for x in xs:
+                    x.copy_(union)
+                sync()
+            outs = [guarded(b.compact_apply, total, bool(kw["want_kept"]) and r == 0) for r, b in enumerate(self.bals)]
+            bad = next((o[1] for o in outs if not o[0]), None)
+        if bad is not None:
+            for b in self.bals:
+                b.compact_cancel()
+            _raise_bad("compact", bad)
+        return [o[1] for o in outs]
 
     def _collective(self, op, kw):
         # phase 1 on every rank, then the summed exchange, then phase 2 / outputs / commit;

@@ -124,6 +124,50 @@ int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
  * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
 int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept);
 
+/* Sharded contexts, between ticks: the group's log renumbered densely by two calls per rank
+ * around one all-reduce ("A shard group's log"), the shape of a sharded tick.
+ *   1. fb_log_compact_shard_mark on every rank: its part of a live bitmap over the global
+ *      sequences [0, log_head), one bit per sequence, into device_buffer;
+ *   2. the ranks all-reduce (SUM over uint8) the first *bytes bytes: the ranks' sequences are
+ *      disjoint, so no byte carries and the sum is the union; they agree on the sum of their
+ *      live counts;
+ *   3. fb_log_compact_shard_apply on every rank with that sum, or fb_log_compact_shard_cancel
+ *      on every rank.
+ * fb_log_compact_shard_bytes: *bytes = the bitmap's size, whole tiles of the global head (8 bytes
+ * per 64 sequences, a multiple of 256; the same on every rank; 0 for an empty log: nothing to
+ * reduce).
+ * fb_log_compact_shard_mark: device_buffer is this GPU's memory, 8-byte aligned, bytes >= that
+ * size.  Every one of the size's bytes is written (bits at or past log_head: 0).  Bit q is set
+ * iff q is the sequence of one of this rank's entries and the entry is live by fb_log_compact's
+ * rule (log_slot[i] >= 0 and, where entries of dead registrations may be in the log, the slot
+ * holds a record and log_seq[i] >= epoch[slot]).  *n_live_local: this rank's live entries.  The
+ * committed state and the tick pipeline stay as they are.  An uncommitted tick is discarded, as
+ * fb_load_shard discards it (a tick waited for and not committed because another rank failed, a
+ * tick whose wait failed): its in-place clears are taken back first, so the entries its results
+ * named count as live.  FB_ESTATE and nothing changes: a one-GPU context (use fb_log_compact),
+ * staged events pending, a tick in flight (phase 1, or launched and not waited for), a mark
+ * already made.
+ * fb_log_compact_shard_apply, after the buffer was reduced in place: counts the reduced bitmap
+ * first (writing only scratch); a count that differs from n_live_global is FB_ESTATE, nothing
+ * changes and the mark is dropped; kept_seq != NULL with cap < n_live_global is FB_EINVAL and
+ * nothing changes.  Otherwise every live local entry keeps its place in the shard's order and
+ * its sequence becomes the number of set bits below it; every own slot's epoch becomes the
+ * number of set bits below min(epoch, log_head); log_head becomes n_live_global and the local
+ * length this rank's live count (*n_kept_local).  kept_seq (may be NULL; cap entries): the GLOBAL
+ * kept list, old sequence of each new sequence, ascending, read off the bitmap (the rank that
+ * serves the dispatcher asks for it; no per-entry gather).  Nothing else changes: records, the
+ * replicated queue, free counts, the tick pipeline's buffers, the round hint, the bound exchange
+ * buffer, the log's address.  FB_ESTATE also: no mark.
+ * fb_log_compact_shard_cancel drops a mark (FB_OK without one).
+ * Between mark and apply / cancel every call that reads or changes the log or launches a tick is
+ * refused with FB_ESTATE.
+ * Replaces nothing in the reference, which keeps no log (README.md:263-264). */
+int fb_log_compact_shard_bytes(fb_ctx *ctx, int64_t *bytes);
+int fb_log_compact_shard_mark(fb_ctx *ctx, void *device_buffer, int64_t bytes, int64_t *n_live_local);
+int fb_log_compact_shard_apply(fb_ctx *ctx, int64_t n_live_global, int64_t *kept_seq, int64_t cap,
+                               int64_t *n_kept_local);
+int fb_log_compact_shard_cancel(fb_ctx *ctx);
+
 /* One-GPU contexts (heartbeat and deque), between ticks: a summary of the committed worker pool
  * at the clock `now`, computed where the state lives (three launches, a few hundred bytes back;
  * DESIGN.md §5e).  A slot is expired iff it is registered and (now - last_heartbeat) > tte, the

@@ -1,0 +1,496 @@
+"""A shard group's log compaction without a GPU.
+
+1. The per-rank numpy model (tests/lcs_model.py: mark, the summed bitmaps, apply) leaves on
+   every rank what tests/lc_model.compact_model leaves of the merged state, split again.
+2. lcs_plan (csrc/faasbal_layout.h), walked on the CPU by tests/lcs_probe.cpp: the grids cover
+   every local entry, every word of the exchange bitmap and every slot exactly once; the
+   scratch regions do not overlap and the mark's regions come first.
+3. The gates (csrc/faasbal_life.h, tests/life_lcs_probe.cpp): the mark's and the apply's at every
+   point of a tick's life, on every context kind; "marked" against every existing call; again
+   under the address and undefined-behaviour sanitizers.
+4. ShardGroup.compact_log over model ranks, in process and over gloo (world 2): the model's
+   result, a wrong ``expect``, a rank whose mark fails.
+5. GpuPushDispatcher over a group of model ranks with a tiny log compacts on the "device".
+"""
+import os
+import shutil
+import socket
+import subprocess
+
+import numpy as np
+import pytest
+
+import life_cases as lc
+import lcs_model as lm
+from faasbal import _lib, synth
+from faasbal._lib import FB_EHIP, FB_ESTATE, FaasbalError
+from faasbal.sharded import shard_range, split_state
+from lc_model import compact_model
+from shard_model_balancer import ModelRankBalancer
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+HEADS = (0, 1, 63, 64, 65, 2047, 2048, 2049, 3 * 2048 + 5)
+
+
+# ------------------------------------------------------------------ 1. the model
+def random_state(rng, W, head, p_done=0.3, p_reg=0.8, epoch_hi=None):
+    """A global state whose log holds completed entries, entries of slots without a record and
+    entries older than their slot's registration."""
+    reg = (rng.random(W) < p_reg).astype(np.uint8)
+    epoch = rng.integers(0, (head if epoch_hi is None else epoch_hi) + 1, W).astype(np.uint32)
+    log = rng.integers(0, W, head).astype(np.int32)
+    log[rng.random(head) < p_done] = -1
+    q = rng.permutation(np.flatnonzero(reg)).astype(np.int32)
+    return dict(reg=reg, free=rng.integers(0, 5, W).astype(np.int32), hb=rng.random(W) + 1000.0, epoch=epoch,
+                queue=q[: len(q) // 2], log=log)
+
+
+def shard_of(st, world, rank):
+    """A rank's part of a global state as the model takes it (dead entries left in the shard)."""
+    d = split_state(st, world, rank)
+    d["head"] = d.pop("log_head")
+    return d
+
+
+def check_group_model(st, world, what):
+    want, kept = compact_model(st)
+    shards = [shard_of(st, world, r) for r in range(world)]
+    outs, got_kept, total = lm.group_model(shards)
+    assert total == len(kept) and np.array_equal(got_kept, kept), what
+    for r, (o, pre) in enumerate(zip(outs, shards)):
+        w = split_state(want, world, r)
+        assert np.array_equal(o["log_slot"], w["log_slot"]) and np.array_equal(o["log_seq"], w["log_seq"]), (what, r)
+        assert np.array_equal(o["epoch"], w["epoch"]) and o["head"] == w["log_head"] == len(kept), (what, r)
+        for k in ("reg", "free", "hb", "queue"):
+            assert np.array_equal(o[k], pre[k]), (what, r, k)
+    return outs, kept
+
+
+@pytest.mark.parametrize("world", (1, 2, 3, 4, 5))
+def test_model_is_compact_model_of_the_merged_state(world):
+    rng = np.random.default_rng(4100 + world)
+    for head in HEADS:
+        for W in (5, 41, 300):
+            check_group_model(random_state(rng, W, head), world, "head %d W %d" % (head, W))
+            # epochs beyond the head too
+            check_group_model(random_state(rng, W, head, epoch_hi=head + 70), world, "head %d W %d far epochs" % (head, W))
+
+
+def test_model_special_cases():
+    rng = np.random.default_rng(4200)
+    # a rank with no slots: W = 5 over 4 ranks is 2 + 2 + 1 + 0
+    assert [shard_range(5, 4, r)[1] for r in range(4)] == [2, 2, 1, 0]
+    outs, _ = check_group_model(random_state(rng, 5, 2049, p_reg=1.0), 4, "zero-slot rank")
+    assert len(outs[3]["log_slot"]) == 0 and len(outs[0]["log_slot"]) > 0
+    # a rank with an empty shard: every entry names a slot of rank 0
+    st = random_state(rng, 40, 300, p_reg=1.0)
+    st["log"] = np.where(st["log"] >= 0, st["log"] % 10, -1).astype(np.int32)
+    outs, kept = check_group_model(st, 4, "empty shards")
+    assert len(kept) > 0 and all(len(o["log_slot"]) == 0 for o in outs[1:])
+    # all live, none live
+    st = random_state(rng, 41, 2049, p_done=0.0, p_reg=1.0, epoch_hi=0)
+    _, kept = check_group_model(st, 3, "all live")
+    assert len(kept) == 2049
+    st = dict(st, log=np.full(2049, -1, np.int32))
+    _, kept = check_group_model(st, 3, "none live")
+    assert len(kept) == 0
+    # epochs at 0, at word and tile boundaries, at the head and beyond it
+    edges = [0, 1, 63, 64, 65, 2047, 2048, 2049, 4095, 4096, 3 * 2048 + 5, 3 * 2048 + 6, 1 << 20]
+    st = random_state(rng, len(edges) * 3, 3 * 2048 + 5, p_reg=1.0)
+    st["epoch"] = np.repeat(np.asarray(edges, np.uint32), 3)
+    for world in (1, 2, 5):
+        check_group_model(st, world, "epoch edges")
+    # the bitmap is whole tiles of the head, and nothing past the head is set
+    for head in HEADS:
+        st = random_state(rng, 17, head)
+        for r in range(2):
+            bits, _ = lm.mark_model(shard_of(st, 2, r))
+            assert len(bits) == 8 * 32 * (-(-head // 2048)) and not np.unpackbits(bits, bitorder="little")[head:].any()
+    # a union that is not the agreed total is refused
+    shards = [shard_of(st, 2, r) for r in range(2)]
+    marks = [lm.mark_model(s) for s in shards]
+    with pytest.raises(FaasbalError) as e:
+        lm.apply_model(shards[0], marks[0][0] + marks[1][0], marks[0][1] + marks[1][1] + 1)
+    assert e.value.code == FB_ESTATE
+
+
+# ------------------------------------------------------------------ 2. the plan
+def _hipcc(tmp, src, name, extra=()):
+    if shutil.which("hipcc") is None:
+        pytest.fail("hipcc not found: %s cannot be compiled" % src)
+    exe = str(tmp / name)
+    subprocess.run(["hipcc", "-std=c++17", "-O1", *extra, "-I" + os.path.join(REPO, "distributed-faas_amd", "csrc"),
+                    "-I" + os.path.join(REPO, "include"), os.path.join(HERE, src), "-o", exe], check=True)
+    return exe
+
+
+def test_plan_covers_entries_words_and_slots_once(tmp_path):
+    exe = _hipcc(tmp_path, "lcs_probe.cpp", "lcs_probe")
+    cases = []
+    for head in HEADS + (1 << 22,):
+        for hl in sorted({0, 1, head // 3, head}):
+            if hl > head:
+                continue
+            for W, k in ((0, 1), (1, 1), (256, 0), (257, 1)):
+                cases.append((head, hl, W, k))
+    text = "".join("%d %d %d %d\n" % c for c in cases)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout
+    rows = [{k: int(v) for k, v in (kv.split("=") for kv in line.split())} for line in out.splitlines()]
+    assert len(rows) == len(cases)
+    for (head, hl, W, want), r in zip(cases, rows):
+        what = "head %d local %d W %d kept %d" % (head, hl, W, want)
+        assert (r["tile"], r["words_per_tile"]) == (2048, 32), what
+        assert r["ntl"] == -(-hl // 2048) and r["ntg"] == -(-head // 2048), what
+        assert r["nwl"] == 32 * r["ntl"] and r["nwg"] == 32 * r["ntg"], what
+        assert r["xbytes"] == 8 * 32 * (-(-head // 2048)) == lm.bitmap_bytes(head), what
+        assert r["flag_grid"] == -(-r["ntl"] // 4) and r["count_grid"] == -(-r["ntg"] // 4), what
+        assert r["mark_grid"] == -(-r["nwg"] // 256) and r["scan_grid"] == 1, what
+        assert r["move_tiles"] == r["flag_grid"] and r["move_slots"] == -(-W // 256), what
+        assert r["move_kept"] == (r["count_grid"] if want else 0), what
+        assert r["move_grid"] == r["move_tiles"] + r["move_slots"] + r["move_kept"], what
+        for k in ("flag.cover", "move.cover", "mark.cover", "count.cover", "kept.cover", "slots.cover", "order"):
+            assert r[k] == 1, (what, k)
+        # the scratch: each region at least what its pass touches, in order, no overlap, 256-byte
+        # aligned; the mark's regions first, `keep` their end
+        need = [("lbitmap", 8 * r["nwl"]), ("lwrel", 4 * r["nwl"]), ("ltcnt", 4 * r["ntl"]), ("ltpre", 4 * (r["ntl"] + 1)),
+                ("gwrel", 4 * r["nwg"]), ("gtcnt", 4 * r["ntg"]), ("gtpre", 4 * (r["ntg"] + 1)), ("dst", 4 * hl),
+                ("dseq", 4 * hl), ("kept", 8 * head if want else 0)]
+        end = 0
+        for key, nbytes in need:
+            assert r[key] >= end and r[key] % 256 == 0, (what, key)
+            end = r[key] + nbytes
+            if key == "ltpre":
+                assert end <= r["keep"] <= r["gwrel"], what
+        assert r["bytes"] >= end, what
+
+
+# ------------------------------------------------------------------ 3. the gates
+MARKED = "a log compaction is marked: apply or cancel first"
+MARK_ONE_GPU = "fb_log_compact_shard_mark on a one-GPU context: use fb_log_compact"
+MARK_STAGED = "fb_log_compact_shard_mark with staged events pending: their sequences would go stale"
+MARK_IN_FLIGHT = "fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first"
+APPLY_ONE_GPU = "fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact"
+APPLY_UNMARKED = "fb_log_compact_shard_apply without fb_log_compact_shard_mark"
+# what touches neither the log nor a tick goes on while a compaction is marked
+MARKED_PASSES = ("exchange_bytes", "debug_read", "sync")
+
+
+def _ask(exe, lines, env=None):
+    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env)
+    assert p.returncode == 0 and not p.stderr, (p.returncode, p.stderr[-2000:])
+    out = p.stdout.splitlines()
+    assert len(out) == len(lines) and not any(a.startswith("error=") for a in out), p.stdout[-2000:]
+    return out
+
+
+def _gates(exe, lines, env=None):
+    res = []
+    for a in _ask(exe, lines, env):
+        head, refuse = a.split(" refuse=", 1)
+        w = dict(x.split("=", 1) for x in head.split())
+        res.append((None if refuse == "-" else refuse, [] if w["duties"] == "-" else w["duties"].split(",")))
+    return res
+
+
+def want_mark(kind, s):
+    """The mark's gate, written from the issue's rules on the state's fields."""
+    staged, pos, _, eager, _, cm, undo_e, _ = s.split(",")
+    flush = ["flush"] if cm == "1" else []
+    if kind != "shard":
+        return MARK_ONE_GPU, flush
+    if staged == "1":
+        return MARK_STAGED, []
+    if pos in ("phase1", "launched") or (pos in ("waited", "failed") and eager == "1"):
+        return MARK_IN_FLIGHT, []
+    # a waited-uncommitted, failed or dropped tick is discarded, its clears taken back first
+    return None, flush + (["undo"] if int(undo_e) > 0 else []) + (["discard"] if pos in ("waited", "failed") else [])
+
+
+def _check_gates(exe, env=None):
+    seen = set()
+    for kind in lc.KINDS:
+        states = list(lc.STATES[kind])
+        got = _gates(exe, ["mark %s %s,0" % (kind, s) for s in states], env)
+        for s, g in zip(states, got):
+            assert g == want_mark(kind, s), (kind, s, g)
+            seen.add((kind == "shard", s.split(",")[1], g[0], tuple(g[1])))
+        # the apply's: only after a mark, only on a sharded context
+        for s, (refuse, duties) in zip(states, _gates(exe, ["apply %s %s,0" % (kind, s) for s in states], env)):
+            assert refuse == (APPLY_UNMARKED if kind == "shard" else APPLY_ONE_GPU), (kind, s)
+            assert duties == (["flush"] if kind != "shard" and s.split(",")[5] == "1" else []), (kind, s)
+    # every position of a tick's life was asked: in flight refused, the others discarded or passed
+    assert (True, "waited", None, ("undo", "discard")) in seen and (True, "waited", None, ("discard",)) in seen
+    assert (True, "failed", None, ("undo", "discard")) in seen and (True, "dropped", None, ("undo",)) in seen
+    assert (True, "none", None, ()) in seen
+    assert (True, "phase1", MARK_IN_FLIGHT, ()) in seen and (True, "launched", MARK_IN_FLIGHT, ()) in seen
+    assert (True, "none", MARK_STAGED, ()) in seen and (True, "waited", MARK_STAGED, ()) in seen
+    # the transitions: a mark leaves no tick and nothing owed, whatever it found; cancel and
+    # apply leave the state a commit leaves
+    for s in lc.STATES["shard"]:
+        refuse, duties = want_mark("shard", s)
+        if refuse is not None:
+            continue
+        ev = (["commit_ran"] if "flush" in duties else []) + (["undone"] if "undo" in duties else []) + ["marked"]
+        after = _ask(exe, ["step shard %s,0 %s" % (s, " ".join(ev))], env)[0]
+        assert after == "0,none,0,0,0,0,0,0,1", (s, after)
+    assert _ask(exe, ["step shard 0,none,0,0,0,0,0,0,1 unmarked", "step shard 0,none,0,0,0,0,0,0,1 replaced"], env) == \
+        ["0,none,0,0,0,0,0,0,0"] * 2
+    # marked: the state a mark leaves, against every existing call, a second mark, the apply and
+    # the rank's part of a pool summary
+    m = "0,none,0,0,0,0,0,0,1"
+    for c, (refuse, duties) in zip(lc.CALLS, _gates(exe, ["gate shard %s %s" % (m, c) for c in lc.CALLS], env)):
+        if c in MARKED_PASSES:
+            assert (refuse, duties) == (None, []), c
+        else:
+            assert (refuse, duties) == (MARKED, []), (c, refuse)
+    assert _gates(exe, ["mark shard " + m, "apply shard " + m, "stats shard " + m], env) == \
+        [(MARKED, []), (None, []), (MARKED, [])]
+    # without a mark the existing calls answer as tests/life_cases.py's table says
+    rows = [(s, c) for s in lc.STATES["shard"] for c in lc.CALLS]
+    by_life = {}
+    for r in lc.closure("shard"):
+        by_life.setdefault(lc.canon("shard", r), r)
+    for (s, c), g in zip(rows, _gates(exe, ["gate shard %s,0 %s" % (s, c) for s, c in rows], env)):
+        assert lc.gate("shard", by_life[s], c) == g, (s, c, g)
+
+
+def test_gates(tmp_path):
+    _check_gates(_hipcc(tmp_path, "life_lcs_probe.cpp", "life_lcs_probe"))
+
+
+def test_gates_sanitized(tmp_path):
+    """Address + undefined-behaviour sanitizers on the host code, as a stand-alone program."""
+    exe = _hipcc(tmp_path, "life_lcs_probe.cpp", "life_lcs_probe_san",
+                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
+    _check_gates(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
+
+
+def test_entry_points_go_through_the_gates():
+    api = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_api.hip")).read()
+    life = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_life.h")).read()
+    assert "life_gate_log_compact_shard_mark(c->life, c->caps)" in api
+    assert "life_gate_log_compact_shard_apply(c->life, c->caps)" in api
+    assert life.count('"%s"' % MARKED) == 1  # stated once
+    assert "X(log_compact_shard" not in life and "log_compact_shard" not in "".join(lc.CALLS)
+    hdr = open(os.path.join(REPO, "include", "faasbal.h")).read()
+    for name in ("bytes", "mark", "apply", "cancel"):
+        assert "int fb_log_compact_shard_%s(" % name in hdr and "fb_log_compact_shard_%s" % name in _lib.EXPORTS
+    assert callable(_lib.load().fb_log_compact_shard_mark)
+
+
+# ------------------------------------------------------------------ 4. the group over model ranks
+def _scenario_state(seed=7311, W=37):
+    scen = synth.random_scenario(seed, W=W, n_ticks=4, max_events=20, max_new=50)
+    st = dict(reg=scen["init_reg"], free=scen["init_free"], hb=scen["init_hb"], epoch=scen["init_epoch"],
+              queue=scen["init_queue"], log=scen["init_log"])
+    return scen, st
+
+
+def _run_ticks(g, scen, ticks, ref, carried=0):
+    """Ticks of a synth scenario on a group, results naming live entries of its state."""
+    for tk in ticks:
+        seq = np.full(len(tk["ev_kind"]), -1, np.int64)
+        for i in np.nonzero(tk["ev_kind"] == synth.EV_RESULT)[0]:
+            mine = np.nonzero(ref["log"] == tk["ev_slot"][i])[0]
+            if len(mine) and tk["ev_pick"][i] % 5 != 4:
+                seq[i] = mine[tk["ev_pick"][i] % len(mine)]
+        n = carried + tk["n_new"]
+        out = g.tick(tk["now"], scen["tte"], tk["ev_kind"], tk["ev_slot"], tk["ev_val"], tk["ev_ts"], seq, n)
+        carried = n + len(out["orphans"]) - len(out["assign"])
+        ref = g.read_state()
+    return ref, carried
+
+
+def _same_state(a, b, keys=("reg", "free", "hb", "epoch", "queue", "log")):
+    return all(np.array_equal(a[k], b[k]) for k in keys) and a["head"] == b["head"]
+
+
+def check_group_compaction(g, n_ranks_read, world, W):
+    """compact_log on a group: the model of the merged state on every rank; returns the state."""
+    pre = g.read_state()
+    want, kept = compact_model(pre)
+    out = g.compact_log(expect=len(kept))
+    assert out["n_kept"] == len(kept) and np.array_equal(out["kept"], kept)
+    post = g.read_state()
+    assert post["head"] == len(kept)
+    for k in ("log", "epoch"):
+        assert np.array_equal(post[k], want[k]), k
+    for k in ("reg", "free", "hb", "queue"):  # (a slot without a record may hold NaN as its heartbeat)
+        np.testing.assert_array_equal(post[k], pre[k], err_msg=k)
+    for r, rs in enumerate(n_ranks_read()):
+        w = split_state(want, world, r)
+        assert np.array_equal(rs["log"], w["log_slot"]) and np.array_equal(rs["log_seq"], w["log_seq"]), r
+        assert np.array_equal(rs["epoch"], w["epoch"]) and rs["head"] == len(kept), r
+    return post
+
+
+@pytest.mark.parametrize("world", (1, 2, 3, 4))
+def test_local_group_compacts_as_the_model(world):
+    scen, st = _scenario_state()
+    W = 37
+    g = lm.ModelGroup(world, W)
+    assert callable(g.compact_log)
+    g.load(st)
+    ref, carried = _run_ticks(g, scen, scen["ticks"][:3], g.read_state())
+    assert (ref["log"] < 0).any() and (ref["log"] >= 0).any()
+    post = check_group_compaction(g, lambda: [b.read_state() for b in g.bals], world, W)
+    assert post["head"] < ref["head"]
+    # without a kept list; then a wrong expect: FB_ESTATE, every rank cancelled, nothing changed
+    assert g.compact_log(want_kept=False) == {"n_kept": post["head"], "kept": None}
+    ref, carried = _run_ticks(g, scen, scen["ticks"][3:], post, carried)
+    before = [b.read_state() for b in g.bals]
+    with pytest.raises(FaasbalError) as e:
+        g.compact_log(expect=int((ref["log"] >= 0).sum()) + 1)
+    assert e.value.code == FB_ESTATE
+    # a rank whose mark raises: all cancel, nothing changes
+    g.bals[-1].fail_mark = True
+    with pytest.raises(FaasbalError) as e:
+        g.compact_log()
+    assert e.value.code == FB_EHIP and "injected" in str(e.value)
+    for b, pre in zip(g.bals, before):
+        assert b.marked is None
+        now = b.read_state()
+        assert all(np.array_equal(now[k], pre[k]) for k in pre if k != "base"), b.rank
+    # ... and the group serves the next tick and compacts
+    g.tick(scen["ticks"][-1]["now"] + 1.0, scen["tte"], n_pending=5)
+    check_group_compaction(g, lambda: [b.read_state() for b in g.bals], world, W)
+
+
+def test_group_of_old_doubles_has_no_device_path():
+    g = lm.ModelGroup(2, 8, ModelRankBalancer)
+    assert g.compact_log is None and g.pool_stats is None
+    from faasbal.sharded import ShardedBalancer
+    assert ShardedBalancer.compact_log is None and callable(ShardedBalancer.compact_mark)
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _gloo_rank(rank, world, port, errq):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+    from faasbal.sharded import DistShardGroup, serve_shard
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        scen, st = _scenario_state()
+        W = 37
+        bal = lm.CompactRank(rank, world, W)
+        if rank != 0:
+            # this rank's fourth mark fails
+            served = [0]
+            mark = bal.compact_mark
+
+            def counted():
+                served[0] += 1
+                bal.fail_mark = served[0] == 4
+                return mark()
+            bal.compact_mark = counted
+            serve_shard(bal)
+            assert served[0] == 5 and bal.marked is None
+            return
+        g = DistShardGroup(bal, W)
+        assert callable(g.compact_log)
+        g.load(st)
+        ref, carried = _run_ticks(g, scen, scen["ticks"][:3], g.read_state())
+        # 1: the model's result (read through the group: every rank's shard)
+        pre = ref
+        want, kept = compact_model(pre)
+        out = g.compact_log(expect=len(kept))
+        assert out["n_kept"] == len(kept) and np.array_equal(out["kept"], kept) and 0 < len(kept) < pre["head"]
+        post = g.read_state()
+        assert _same_state(post, dict(want, head=len(kept)))
+        # 2: without the kept list
+        assert g.compact_log(want_kept=False) == {"n_kept": len(kept), "kept": None}
+        ref, carried = _run_ticks(g, scen, scen["ticks"][3:], post, carried)
+        # 3: a wrong expect: FB_ESTATE, every shard unchanged
+        try:
+            g.compact_log(expect=int((ref["log"] >= 0).sum()) + 1)
+            raise AssertionError("a wrong expect was accepted")
+        except FaasbalError as e:
+            assert e.code == FB_ESTATE, e
+        assert _same_state(g.read_state(), ref) and bal.marked is None
+        # 4: rank 1's mark raises: every rank still reaches the collective, all cancel
+        try:
+            g.compact_log()
+            raise AssertionError("the failing rank's error did not reach rank 0")
+        except FaasbalError as e:
+            assert e.code == FB_EHIP and "injected" in str(e), e
+        assert _same_state(g.read_state(), ref) and bal.marked is None
+        # ... the group serves the next tick, and compacts (5)
+        g.tick(scen["ticks"][-1]["now"] + 1.0, scen["tte"], n_pending=5)
+        pre = g.read_state()
+        want, kept = compact_model(pre)
+        out = g.compact_log(expect=len(kept))
+        assert np.array_equal(out["kept"], kept) and _same_state(g.read_state(), dict(want, head=len(kept)))
+        g.close()
+    except Exception as e:  # report to the parent, keep the peer from hanging
+        errq.put("rank %d: %r" % (rank, e))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_dist_shard_group_compacts_over_gloo():
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    errq = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_gloo_rank, args=(r, 2, port, errq)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(240)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+    errs = []
+    while not errq.empty():
+        errs.append(errq.get())
+    assert not errs, errs
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+
+
+# ------------------------------------------------------------------ 5. the dispatcher
+def group_dispatcher(world, rank_cls):
+    """A constructor in GpuPushDispatcher's place: the dispatcher over a group of ``rank_cls``
+    model ranks (tests/test_log_compact_host.py's scenarios take it)."""
+    from faasbal.dispatcher import GpuPushDispatcher
+
+    def make(host, port, tte, **kw):
+        W = kw["max_workers"]
+        group = lm.ModelGroup(world, W, rank_cls)
+        d = GpuPushDispatcher(host, port, tte, balancer=group, **kw)
+        group.calls = calls = dict(read_log=0, load=0, compact=0)
+        read, load, compact = group.read_state, group.load_state, group.compact_log
+        group.read_state = lambda with_log=True: (calls.__setitem__("read_log", calls["read_log"] + bool(with_log)),
+                                                  read(with_log))[1]
+        group.load_state = lambda *a, **k: (calls.__setitem__("load", calls["load"] + 1), load(*a, **k))[1]
+        if compact is not None:
+            group.compact_log = lambda **k: (calls.__setitem__("compact", calls["compact"] + 1), compact(**k))[1]
+        return d
+    return make
+
+
+@pytest.mark.parametrize("world", (2, 3))
+@pytest.mark.parametrize("name", ("small_log", "backlog", "enospc"))
+def test_dispatcher_compacts_a_group_on_the_device(name, world):
+    from test_log_compact_host import SCENARIOS
+    run, cap = SCENARIOS[name]
+    big, d0 = run(group_dispatcher(world, lm.CompactRank), 1 << 16)
+    small, d = run(group_dispatcher(world, lm.CompactRank), cap)
+    assert d0.compactions == 0 and small == big and sum(len(x) for x in big) > 50
+    assert d.device_compactions == d.compactions > 0
+    calls = d.balancer.calls
+    # no log read, no reload: the dispatcher only remapped its two dicts from the kept list
+    assert calls == dict(read_log=0, load=0, compact=d.compactions)
+    log = d.balancer.read_state()["log"]
+    assert d.head == len(log) and all(0 <= q < d.head and log[q] == s for q, (_, s) in d.inflight.items())
+    # a group of ranks without the parts keeps the host path, with the same messages
+    host, h = run(group_dispatcher(world, ModelRankBalancer), cap)
+    assert host == big and h.compactions > 0 and h.device_compactions == 0
+    assert h.balancer.calls["read_log"] == h.compactions == h.balancer.calls["load"]
