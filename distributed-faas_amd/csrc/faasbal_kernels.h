@@ -89,7 +89,8 @@ constexpr int kGrpWords = 64 * 260;
 constexpr int kShardMaxR = 4096;     // sharded round tables (k_emit_shard_wide: 64 chunks of 64 rounds)
 
 // event kinds / status (include/faasbal.h)
-constexpr int kEvRegister = 0, kEvReconnect = 1, kEvHeartbeat = 2, kEvResult = 3, kEvOther = 4;
+constexpr int kEvRegister = 0, kEvReconnect = 1, kEvHeartbeat = 2, kEvResult = 3, kEvOther = 4,
+              kEvLeave = 5;
 constexpr uint8_t kEvsApplied = 0, kEvsReconnect = 1;
 
 // deque mode (PushDispatcher.start): a committed token rank with this bit set sat in

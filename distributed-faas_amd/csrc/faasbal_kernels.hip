@@ -678,8 +678,10 @@ struct SlotRun {
     __device__ __forceinline__ bool step(const EvArgs &a, uint32_t gs, int i, int kind, int32_t val, double ts,
                                          int64_t seq, int32_t logv = 0, bool dup = false) {
         bool cleared = false;
-        // purge at ts before the message is polled (:390 of the previous iteration)
-        if (reg && (ts - hb) > a.tte) {
+        // purge at ts before the message is polled (:390 of the previous iteration); a leave
+        // (the goodbye) is that deletion forced: the record goes whatever its heartbeat says
+        const bool leave = kind == kEvLeave;
+        if (reg && (leave || (ts - hb) > a.tte)) {
             reg = 0;
             inq = 0;
             qstat = kQsOut;
@@ -692,8 +694,12 @@ struct SlotRun {
             fr = val;
             if (val > 0) { inq = 1; qstat = kQsFront; qidx = i; }
         } else if (!reg) {                               // :356-358 unknown id
-            reg = 1; epoch = a.head_in; hb = ts; fr = 0;
-            status = kEvsReconnect;
+            // (not a leave, whose slot holds no record by now: a goodbye creates no worker
+            // and asks for no reconnect)
+            if (!leave) {
+                reg = 1; epoch = a.head_in; hb = ts; fr = 0;
+                status = kEvsReconnect;
+            }
         } else if (kind == kEvReconnect) {               // :360-367
             hb = ts;
             fr = val;
@@ -959,7 +965,7 @@ __global__ __launch_bounds__(kBS) void k_ev_link(EvArgs a) {
             // heartbeat) for the rest of the launch, whose tick the host then refuses
             const uint8_t k = a.ev_kind[t];
             const double tt = a.ev_ts[t], tp = a.ev_ts[t > 0 ? t - 1 : 0];
-            const bool bad_sk = s >= (uint32_t)a.W || k > kEvOther;
+            const bool bad_sk = s >= (uint32_t)a.W || k > kEvLeave;
             if (bad_sk || !(tt <= a.now) || tt < tp) {
                 a.hout->bad_ev = 1;
                 if (a.cw) a.cw[0] = a.link;

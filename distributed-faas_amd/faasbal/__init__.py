@@ -10,4 +10,4 @@ from .balancer import GpuBalancer  # noqa: F401
 from .dispatcher import GpuPushDispatcher  # noqa: F401
 from . import synth  # noqa: F401
 
-EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER = 0, 1, 2, 3, 4
+EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER, EV_LEAVE = 0, 1, 2, 3, 4, 5

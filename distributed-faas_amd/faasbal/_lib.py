@@ -12,6 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libfaasbal.so")
 
+FB_EV_REGISTER, FB_EV_RECONNECT, FB_EV_HEARTBEAT, FB_EV_RESULT, FB_EV_OTHER, FB_EV_LEAVE = 0, 1, 2, 3, 4, 5
 FB_EVS_APPLIED, FB_EVS_RECONNECT, FB_EVS_UNKNOWN = 0, 1, 2
 FB_OK, FB_EINVAL, FB_ENOMEM, FB_EHIP, FB_ERANGE, FB_ENOSPC, FB_ESTATE, FB_ERERUN = 0, -1, -2, -3, -4, -5, -6, -7
 ERRNAMES = {FB_EINVAL: "FB_EINVAL", FB_ENOMEM: "FB_ENOMEM", FB_EHIP: "FB_EHIP", FB_ERANGE: "FB_ERANGE",

@@ -50,8 +50,10 @@ from ._lib import FB_ENOSPC, FB_ESTATE, FB_EVS_RECONNECT, FaasbalError
 from .balancer import GpuBalancer
 from .poolstats import pool_stats_model
 
-EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER = 0, 1, 2, 3, 4
-_KINDS = {"register": EV_REGISTER, "reconnect": EV_RECONNECT, "heartbeat": EV_HEARTBEAT, "result": EV_RESULT}
+EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER, EV_LEAVE = 0, 1, 2, 3, 4, 5
+# {"type": "leave"}: a worker's goodbye (FB_EV_LEAVE, include/faasbal.h); the reference's workers never send it
+_KINDS = {"register": EV_REGISTER, "reconnect": EV_RECONNECT, "heartbeat": EV_HEARTBEAT, "result": EV_RESULT,
+          "leave": EV_LEAVE}
 _I32 = (-(1 << 31), (1 << 31) - 1)
 
 
@@ -165,6 +167,7 @@ class GpuPushDispatcher:
         self.pending = collections.deque()             # task ids not yet dispatched (orphans first)
         self.head = 0                                  # in-flight log length
         self._last_ts = -np.inf
+        self._leaving = collections.deque()            # identities evict() asked to remove, for the next tick
 
     # ------------------------------------------------ reference socket / Redis API
     def bind_socket(self):
@@ -235,6 +238,9 @@ class GpuPushDispatcher:
 
     def _drain_inbound(self):
         msgs = []
+        # the operator's goodbyes (evict()) ahead of this tick's ZMQ messages
+        while self._leaving and len(msgs) < self.max_events:
+            msgs.append((self._leaving.popleft(), {"type": "leave"}, self._stamp()))
         while len(msgs) < self.max_events and self._inbound_ready():
             worker_id, message = self.receive_message()
             msgs.append((worker_id, message, self._stamp()))
@@ -272,6 +278,32 @@ class GpuPushDispatcher:
                 (keep if wid in known else unknown).append(x)
         return keep, unknown
 
+    def _drop_unknown_leaves(self, msgs):
+        """A leave from an identity without a slot -- none before the tick and no earlier
+        message in the batch that gives it one -- is dropped: no slot means no record, so
+        there is nothing to delete, and a goodbye must not allocate a slot."""
+        keep, new = [], set()
+        for x in msgs:
+            wid, m, _t = x
+            if wid not in self.slot_of and wid not in new:
+                if isinstance(m, dict) and m.get("type") == "leave":
+                    continue
+                new.add(wid)
+            keep.append(x)
+        return keep
+
+    def evict(self, worker_ids):
+        """Take workers out of the pool on the operator's word: a synthetic
+        ``{"type": "leave"}`` per identity, applied by the next tick ahead of its ZMQ
+        messages (they count against ``max_events``).  That tick deletes the records,
+        releases the identities and puts the workers' in-flight tasks at the front of the
+        pending ones, exactly as for a leave the worker sent itself; a later message from
+        such an identity is answered with ``reconnect``.  The same on one GPU and on a shard
+        group (it is only messages).  Returns the identities that had a slot."""
+        worker_ids = list(worker_ids)
+        self._leaving.extend(worker_ids)
+        return [w for w in worker_ids if w in self.slot_of]
+
     def _run(self, msgs):
         # room for every dispatch this tick can make (orphans + pending) before sequence
         # numbers are taken.  Compaction reclaims the finished entries (head - in-flight);
@@ -289,7 +321,9 @@ class GpuPushDispatcher:
         arrived = msgs
         unknown = []
         if self.mode == "deque":
-            msgs, unknown = self._deque_filter(msgs)
+            msgs, unknown = self._deque_filter(msgs)  # (register and result only: a leave is ignored)
+        else:
+            msgs = self._drop_unknown_leaves(msgs)
         E = len(msgs)
         kind = np.empty(E, np.uint8)
         slot = np.empty(E, np.int32)
@@ -347,8 +381,8 @@ class GpuPushDispatcher:
         for x in arrived:
             wid, m, _ = x
             i = index.get(id(x))
-            if i is None:  # deque loop: result from an identity without a record
-                if m.get("type") == "result":
+            if i is None:  # deque loop: result from an identity without a record (or a dropped leave)
+                if isinstance(m, dict) and m.get("type") == "result":
                     data = m["data"]
                     rdb.hset(data["task_id"], mapping={"status": data["status"], "result": data["result"]})
                 continue

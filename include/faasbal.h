@@ -38,6 +38,30 @@ extern "C" {
 #define FB_EV_HEARTBEAT 2  /* {"type":"heartbeat"}                              */
 #define FB_EV_RESULT 3     /* {"type":"result", ...}; seq = task's log sequence */
 #define FB_EV_OTHER 4      /* any other type: ignored for known workers         */
+/* {"type":"leave"}: the worker's goodbye (absent from the reference, whose only way
+ * out is an expired heartbeat).  One leave at clock ts from slot s:
+ *   - Purge first.  The purge at ts runs before it, as before every message (:390 of
+ *     the previous iteration).
+ *   - s holds a record: the record is deleted exactly as that purge deletes an
+ *     expired one -- the record is gone, the slot is out of the LRU queue, and a
+ *     registration that existed at tick start counts as died-at-start: its in-flight
+ *     entries (sequence >= its epoch) are this tick's orphans, dispatched first.
+ *   - Later messages of s in the same tick meet an unknown identity: a register opens
+ *     a new registration (epoch = the log head at tick start), anything else creates
+ *     the free = 0 record and is answered with FB_EVS_RECONNECT (:356-358).
+ *   - s holds no record at that point (it never had one, it expired at ts, it already
+ *     left): nothing happens.  No record is created and no reconnect is asked for --
+ *     a goodbye must not create the worker.
+ *   - The status is FB_EVS_APPLIED in both cases; val and seq are ignored.
+ *   - The evicted list keeps its rule: a slot is listed when it held a record at tick
+ *     start or got any message in the tick, and holds no record after the tick.  So a
+ *     leave from a slot that never had a record lists that slot -- which is how a host
+ *     mirror that gave the sender a slot number gets it back.
+ *   - With a finite tte a leave equals overwriting the record's heartbeat with
+ *     ts - tte - 1; it is not done that way, and works with tte = +inf too.
+ *   - Deque contexts (no liveness, records never deleted) refuse a batch that holds a
+ *     leave at stage: FB_EINVAL, "event %d: leave on a deque context", nothing staged. */
+#define FB_EV_LEAVE 5
 
 /* Per-event status written by a tick. */
 #define FB_EVS_APPLIED 0
