@@ -433,6 +433,8 @@ struct Timer {
     }
 };
 
+static_assert(kMaxR == FB_MAX_ROUNDS && kShardMaxR == FB_MAX_ROUNDS, "the round range include/faasbal.h states");
+
 int ensure_table(fb_ctx *c, int R, int nbq) {
     size_t need = (size_t)R * (size_t)nbq;
     if (need > c->table_cap) {
@@ -1734,6 +1736,7 @@ int fb_load_shard(fb_ctx *c, int32_t slot_base, int32_t n_workers, const uint8_t
     // (maxc above) would differ between ranks.  A fill level beyond it relaunches wider.
     (void)maxc;
     c->maxc_hint = 1;
+    c->shard_R = 0;  // (a wide table kept for the replaced state's fill level, or asked by its relaunch)
     life_replaced(c->life);
     return FB_OK;
 }
@@ -2669,8 +2672,8 @@ static int tick_wait(fb_ctx *c, fb_tick_result *res, Wait &o) {
     // the queue holds free counts beyond the round table: widen and rerun
     if (c->hout->status != 0 && c->shard) {
         // the exchange runs between the phases, so the caller relaunches: the same tick
-        // with a table sized by the max free count seen (clamped to the exchange width)
-        const int R = choose_R(c->hout->maxc);
+        // with a table sized by the max free count seen (the ranks' records carry the true one)
+        const int R = choose_R(c->hout->maxc, kShardMaxR);
         o = Wait::too_narrow;
         if (c->l_R >= kShardMaxR || R <= c->l_R)
             return fail(c, FB_ERANGE, "sharded tick: fill level beyond a %d-round table (max free %d)", c->l_R,

@@ -87,6 +87,11 @@ constexpr int kLsBS = 1024;        // k_logscan: one 16-wave workgroup per CU
 // group rows of round totals (<= 64 groups x (R + 4) words; sharded phase 2: x (2 R + 4))
 constexpr int kGrpWords = 64 * 260;
 constexpr int kShardMaxR = 4096;     // sharded round tables (k_emit_shard_wide: 64 chunks of 64 rounds)
+// one GPU: the widest round table a tick is given (choose_R saturates here).  A tick is exact
+// while its fill level L <= kMaxR - 2, whatever the free counts; one that needs more fails
+// with FB_ERANGE (include/faasbal.h).  No test, golden vector or benchmark shape reaches a
+// fill level beyond a few hundred rounds, so the sharded limit serves here too.
+constexpr int kMaxR = 4096;
 
 // event kinds / status (include/faasbal.h)
 constexpr int kEvRegister = 0, kEvReconnect = 1, kEvHeartbeat = 2, kEvResult = 3, kEvOther = 4,

@@ -1943,9 +1943,11 @@ __global__ __launch_bounds__(kBS, (WT == 4 ? 8 : 1)) void k_scan(TickArgs a_) {
                 if (r < kBS) wc[w][r] = r <= R ? 64u - P : 0u;
                 carry = (uint32_t)__builtin_amdgcn_readlane((int)P, 63);
             }
-            // max c (the byte's clamp, as exchanged) into word 1 of one of the rank's record
-            // lines (8 lines: same-line device atomics serialise)
-            const uint32_t wmx = wave_max_u32((uint32_t)(c < 255 ? c : 255));
+            // max c into word 1 of one of the rank's record lines (8 lines: same-line device
+            // atomics serialise).  The count itself, not the exchanged byte's clamp: only this
+            // rank writes its record, so the exchange's byte sums carry any value, the result's
+            // max_free is the true one and a relaunch gets the table it needs at once
+            const uint32_t wmx = wave_max_u32((uint32_t)c);
             if (lane == 0) m4[w] = (int32_t)wmx;
             lds_barrier();
             const int xs = xr_stride(R), t = threadIdx.x;
@@ -1996,6 +1998,17 @@ __global__ __launch_bounds__(kBS, (WT == 4 ? 8 : 1)) void k_scan(TickArgs a_) {
                     }
                     if (t == 0) a.xg_tk[g] = 0u;
                 }
+            }
+        } else if (a.xcw == 2) {
+            // a relaunch with a wide table (two-byte counts, clamped at 65 535): the true max c
+            // into the rank's record as above, for k_plan's totals
+            const uint32_t wmx = wave_max_u32((uint32_t)c);
+            if (lane_id() == 0) m4[wave_id()] = (int32_t)wmx;
+            lds_barrier();
+            if (threadIdx.x == 0) {
+                const int32_t bm = max(max(m4[0], m4[1]), max(m4[2], m4[3]));
+                if (bm > 0)
+                    atomicMax(&a.xrec[a.rank * kXRecWords + (b & (kXRecLines - 1)) * 16 + 1], (unsigned long long)bm);
             }
         }
         STAMP(a, SO, 15);
@@ -2360,9 +2373,13 @@ __global__ __launch_bounds__(kBS) void k_plan(TickArgs a) {
         unsigned long long sum = 0;
         // sharded: the ranks' orphan-count partials (kXRecLines per rank), one load per
         // thread issued up front -- a serial loop over them costs a round trip each
-        uint32_t op = 0;
+        uint32_t op = 0, xmx = 0;
         if (a.shard)
-            for (int g = threadIdx.x; g < a.world * kXRecLines; g += kBS) op += (uint32_t)a.xrec[(size_t)g * 16];
+            for (int g = threadIdx.x; g < a.world * kXRecLines; g += kBS) {
+                op += (uint32_t)a.xrec[(size_t)g * 16];
+                // (two-byte counts: the ranks' true max c beside the clamped one of the c values)
+                if (a.xcw == 2) xmx = max(xmx, (uint32_t)a.xrec[(size_t)g * 16 + 1]);
+            }
         for (int i0 = 0; i0 < a.nbq; i0 += 8 * kBS) {
             int32_t m[8];
             unsigned long long cs[8];
@@ -2382,6 +2399,7 @@ __global__ __launch_bounds__(kBS) void k_plan(TickArgs a) {
         __shared__ uint32_t ow[kWaves];
         op = wave_sum_u32(op);
         if (lane_id() == 0) ow[wave_id()] = op;
+        mx = mx > (int32_t)xmx ? mx : (int32_t)xmx;
         mx = block_reduce_max<int32_t>(mx, m4);
         unsigned long long tot;
         block_excl_scan<unsigned long long>(sum, l4, tot);

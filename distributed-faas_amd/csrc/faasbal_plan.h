@@ -130,9 +130,13 @@ inline XLayout xlayout(int world, int64_t E, int64_t Qlog, int xcw = 1, size_t r
 }
 inline int xc_width(int R) { return R > kRFused ? 2 : 1; }
 
-inline int choose_R(int32_t maxc) {
+// The rows of the round table for a largest free count: the smallest power of two >= 32 that
+// holds it, saturating at `limit` (a power of two: kMaxR, sharded kShardMaxR) -- any int32
+// ends the loop, and a count beyond the limit gets the limit's table, which is exact while
+// the fill level leaves two rows (L <= limit - 2)
+inline int choose_R(int32_t maxc, int limit = kMaxR) {
     int R = 32;
-    while (R < maxc) R <<= 1;
+    while (R < maxc && R < limit) R <<= 1;
     return R;
 }
 

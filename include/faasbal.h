@@ -25,7 +25,18 @@ extern "C" {
 #define FB_EINVAL (-1)  /* bad argument or inconsistent state                 */
 #define FB_ENOMEM (-2)  /* device or host allocation failed                  */
 #define FB_EHIP (-3)    /* HIP runtime error                                  */
-#define FB_ERANGE (-4)  /* free counts beyond the supported round range       */
+#define FB_ERANGE (-4)  /* a fill level beyond the supported round range: the round table has
+                         * at most FB_MAX_ROUNDS rows on every context kind.  Any int32 free
+                         * count or message value is accepted by fb_load_state / fb_load_shard /
+                         * fb_tick_stage, and a tick is exact whenever its fill level L (full
+                         * rounds dispatched, fb_tick_result.fill_level) is <= FB_MAX_ROUNDS - 2,
+                         * however large the free counts.  A tick that would need more rows
+                         * fails its fb_tick_wait with FB_ERANGE: it commits nothing, the
+                         * committed state stays readable and unchanged, and the next launch
+                         * runs normally.  No call hangs, overflows or allocates a round table
+                         * beyond FB_MAX_ROUNDS rows per 256 queue positions.  (Also: the
+                         * compact output form past 255 rounds, see fb_set_compact.) */
+#define FB_MAX_ROUNDS 4096
 #define FB_ENOSPC (-5)  /* in-flight log full                                 */
 #define FB_ESTATE (-6)  /* call out of order (e.g. wait without launch): DESIGN.md §5f,
                          * "The life of a tick", has every call at every point of a tick */
@@ -78,7 +89,11 @@ typedef struct fb_tick_result {
     int64_t log_head;    /* log length after the tick: task k got sequence log_head_in+k  */
     int32_t n_evicted;   /* worker records deleted by the tick (purge_workers, :241-249)  */
     int32_t fill_level;  /* water-filling rounds completed (L)                            */
-    int32_t max_free;    /* largest effective free count in the queue this tick           */
+    int32_t max_free;    /* largest effective free count in the queue this tick (sharded:
+                          * the true count too, although the ranks exchange the counts clamped
+                          * to one or two bytes -- except the narrow launches that re-count the
+                          * exchanged bytes, more than 16 ranks or more than 256 queue blocks
+                          * without exchanged rows, which report at most 255)              */
     int32_t reruns;      /* internal reruns with a wider round table                      */
     int64_t n_local;         /* sharded: tasks dispatched to this rank's workers (else n_assigned) */
     int64_t n_orphans_local; /* sharded: orphans from this rank's log shard (else n_orphans)       */
@@ -302,7 +317,12 @@ int fb_tick_launch_staged(fb_ctx *ctx, double tte, int64_t n_pending);
 int fb_purge_launch(fb_ctx *ctx, double now, double tte);
 
 /* Wait for the last launched tick; fills *res.  Transparently reruns the tick
- * with a wider round table when free counts exceeded the launch's estimate. */
+ * with a wider round table when free counts exceeded the launch's estimate (a sharded
+ * context returns FB_ERERUN instead: relaunch).  The table grows to FB_MAX_ROUNDS rows
+ * and no further: a tick whose fill level is <= FB_MAX_ROUNDS - 2 is exact for any int32
+ * free counts; one that needs more rows fails with FB_ERANGE (on every rank of a sharded
+ * group alike), commits nothing and leaves the committed state as it was -- launch a
+ * smaller tick (fewer pending tasks) next. */
 int fb_tick_wait(fb_ctx *ctx, fb_tick_result *res);
 
 /* Make the waited tick's post-state the committed state.  On a one-GPU

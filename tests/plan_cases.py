@@ -126,9 +126,12 @@ LDS_BITMAP_SLOTS = 1 << 17   # kLdsBitmapSlots: contexts up to this size keep in
 R_FUSED = 128                # kRFused: a sharded tick starts with at most this many rows
 
 
-def choose_R(maxc):
+ROW_LIMIT = 4096             # kMaxR / kShardMaxR: the widest round table (choose_R saturates here)
+
+
+def choose_R(maxc, limit=ROW_LIMIT):
     R = 32
-    while R < maxc:
+    while R < maxc and R < limit:
         R <<= 1
     return R
 

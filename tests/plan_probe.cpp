@@ -7,6 +7,9 @@
 //                    the exchange layout as fb_exchange_bytes sizes it (exchange_rows) and
 //                    as plan_tick lays it out for phase 1 of the same shape
 //   knobs            the fb_set_path table: name=allowed values
+//   choose_R maxc=.. [shard=1]
+//                    the round table's rows for a largest free count, and the row limit it
+//                    saturates at (kMaxR; shard=1: kShardMaxR)
 //   layout k=v ...   the plan of a PlanIn, then every multi-role kernel it launches walked
 //                    through its layout (csrc/faasbal_layout.h): "<kernel>.grid", ".n" (the
 //                    workgroups per role), ".pad" and ".cover" (1: workgroups 0 .. grid-1 gave
@@ -210,8 +213,8 @@ int main() {
         WindowIn w{};
         LayoutArgs lay;
         std::string kernel;
-        long long world = 1, R = 32, Qlog = 0, E = 0, xplan = 1;
-        bool ok = cmd == "plan" || cmd == "window" || cmd == "xbytes" || cmd == "knobs" || cmd == "layout" || cmd == "walk";
+        long long world = 1, R = 32, Qlog = 0, E = 0, xplan = 1, maxc = 0, shard = 0;
+        bool ok = cmd == "choose_R" || cmd == "plan" || cmd == "window" || cmd == "xbytes" || cmd == "knobs" || cmd == "layout" || cmd == "walk";
         while (ok && ss >> kv) {
             const size_t eq = kv.find('=');
             if (eq == std::string::npos) {
@@ -225,6 +228,8 @@ int main() {
             else if (cmd == "walk" && key == "kernel") kernel = kv.substr(eq + 1);
             else if (cmd == "walk") ok = set_layout_field(lay, key, v);
             else if (cmd == "window") ok = set_window_field(w, key, v);
+            else if (cmd == "choose_R" && key == "maxc") maxc = v;
+            else if (cmd == "choose_R" && key == "shard") shard = v;
             else if (key == "world") world = v;
             else if (key == "R") R = v;
             else if (key == "Qlog") Qlog = v;
@@ -237,7 +242,11 @@ int main() {
             if (kv.empty()) std::printf("error=bad_request\n");
             continue;
         }
-        if (cmd == "plan") {
+        if (cmd == "choose_R") {
+            const int limit = shard ? kShardMaxR : kMaxR;
+            std::printf("R=%d limit=%d\n", choose_R((int32_t)maxc, limit), limit);
+            std::fflush(stdout);
+        } else if (cmd == "plan") {
             TickArgs a{};
             TickPlan p;
             plan_tick(in, a, p);

@@ -13,6 +13,8 @@ the plan of each request.
    2. and for sweeps around the places where the arithmetic can go wrong.  The dynamic LDS
    a plan requests fits the device's, and plan_window answers as it did when it tested its
    own spelling of k_logscan's bitmap size.
+5. choose_R ends for every int32 and saturates at the row limit (kMaxR, sharded kShardMaxR),
+   and the plans of a table at the limit stay inside the table cap or name a PlanError.
 """
 import collections
 import os
@@ -36,13 +38,14 @@ def probe(tmp_path_factory):
     subprocess.run(["hipcc", "-std=c++17", "-O1", "-I" + os.path.join(REPO, "distributed-faas_amd", "csrc"),
                     "-I" + os.path.join(REPO, "include"), os.path.join(HERE, "plan_probe.cpp"), "-o", exe], check=True)
 
-    def raw(text):
-        return subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout
+    def raw(text, timeout=60):
+        # (a time limit: a request that never ends fails its test instead of stalling the run)
+        return subprocess.run([exe], input=text, capture_output=True, text=True, check=True, timeout=timeout).stdout
 
-    def ask(requests):
+    def ask(requests, timeout=60):
         """One answer dict per request line ("cmd k=v ..." or (cmd, {k: v}))."""
         lines = [r if isinstance(r, str) else r[0] + "".join(" %s=%d" % kv for kv in r[1].items()) for r in requests]
-        out = raw("\n".join(lines) + "\n")
+        out = raw("\n".join(lines) + "\n", timeout)
         ans = [dict(w.split("=", 1) for w in ln.split()) for ln in out.splitlines()]
         assert len(ans) == len(lines), out
         for a, ln in zip(ans, lines):
@@ -375,3 +378,72 @@ def test_xcfirst_defaults_on_at_the_knob_shapes(probe):
             n += 1
     assert n == 2 * (3 + sum(m[0] == "xplan" for m in sf.LADDER_FORMS))
 
+
+
+# ------------------------------------------------------------------ 5. the round range
+INT32_MAX = (1 << 31) - 1
+
+
+def _choose_R(probe, maxc, shard=0):
+    """(R, limit) -- each request in a process of its own under a time limit, so a loop that
+    never ends fails here."""
+    a = probe.raw("choose_R maxc=%d shard=%d\n" % (maxc, shard), timeout=10).split()
+    a = dict(w.split("=", 1) for w in a)
+    return int(a["R"]), int(a["limit"])
+
+
+@pytest.mark.parametrize("shard", [0, 1])
+def test_choose_R_ends_and_saturates(probe, shard):
+    """For every largest free count an int32 can hold: a power of two, monotone in maxc, at
+    least min(maxc, limit) and never beyond the limit (include/faasbal.h: FB_ERANGE)."""
+    limit = _choose_R(probe, 1, shard)[1]
+    assert limit == 4096
+    assert pc.ROW_LIMIT == limit
+    last = 0
+    for maxc in (1, 31, 32, 33, limit - 1, limit, limit + 1, 1 << 30, (1 << 30) + 1, INT32_MAX):
+        R, lim = _choose_R(probe, maxc, shard)
+        assert lim == limit
+        assert R >= 32 and R & (R - 1) == 0, (maxc, R)
+        assert R >= last, (maxc, R, last)
+        assert min(maxc, limit) <= R <= limit, (maxc, R)
+        assert R == pc.choose_R(maxc), (maxc, R)
+        last = R
+    # (values an int32 holds but no free count should: the loop ends all the same)
+    for maxc in (0, -1, -INT32_MAX - 1):
+        assert _choose_R(probe, maxc, shard)[0] == 32
+
+
+def test_plans_at_the_row_limit(probe):
+    """A table of the limit's rows is planned like any other wide table -- no PlanError on one
+    GPU nor in either sharded phase, within limit x nbq entries -- and a sharded table beyond
+    the limit is the PlanError the host turns into FB_ERANGE, never a launch."""
+    limit = pc.ROW_LIMIT
+    for W in (40, 600, 70000):
+        base = dict(pc.DEVICE, W=W, W_global=W, head=4 * W, Qn=W, T=W * (limit - 2))
+        for maxc in (limit, limit + 1, (1 << 30) + 1, INT32_MAX):
+            R = _choose_R(probe, maxc)[0]
+            assert R == limit
+            one = probe([("plan", dict(base, R=R, lists=1, qaos=1, heartbeat=1))], timeout=10)[0]
+            assert one["err"] == "0" and _stages(one) == ["scan", "plan", "emit"], one
+            assert (one["fused"], one["segw"]) == ("0", "0")  # the chunked k_emit
+            for phase, want in ((1, ["scan"]), (2, ["scan2", "plan", "emit"])):
+                sh = probe([("plan", dict(base, R=R, shard=1, world=2, phase=phase, head_local=2 * W))], timeout=10)[0]
+                assert sh["err"] == "0" and _stages(sh) == want, sh
+        over = probe([("plan", dict(base, R=2 * limit, shard=1, world=2, phase=2, head_local=2 * W))], timeout=10)[0]
+        assert over["err"] == "3" and "emit" not in _stages(over), over  # PlanError::shard_rows
+
+
+def test_fill_seam_shapes(probe):
+    """The shapes tests/test_gpu_fill_seams.py relies on: 600 workers keep every table of at
+    most 128 rows fused, the large case is unfused at 128 rows by itself (group rows reduced by
+    k_emit2, no k_plan2), and tables beyond 128 rows take k_plan and the chunked k_emit."""
+    import fill_cases as fc
+    base = dict(pc.DEVICE, lists=1, qaos=1, heartbeat=1)
+    small = dict(base, W=600, W_global=600, head=1200, Qn=600, T=1000)
+    for R, fused in ((32, "1"), (64, "1"), (128, "1"), (256, "0"), (4096, "0")):
+        a = probe([("plan", dict(small, R=R))])[0]
+        assert (a["fused"], a["segw"]) == (fused, fused), (R, a)
+        assert ("plan" in _stages(a)) == (R > 128), (R, a)
+    W = fc.UNFUSED_W
+    a = probe([("plan", dict(base, W=W, W_global=W, head=2 * W, Qn=W, T=W, R=128))])[0]
+    assert (a["fused"], a["segw"], a["gp"]) == ("0", "1", "1") and "plan" not in _stages(a), a
