@@ -1758,85 +1758,12 @@ int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {
     return FB_OK;
 }
 
-// The log renumbered densely on the device (DESIGN.md §5d): count first
-// (k_lc_flag, k_lc_scan write only the scratch), synchronise, check, and only then move.
-int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept) {
-    if (!c) return FB_EINVAL;
-    if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
-    // (a discarded tick's results completed nothing: its clears are taken back before the count)
-    if (int rc_ = enter(c, Call::log_compact)) return rc_;
-    HIPCHK(c, hipSetDevice(c->device));
-    const LcPlan p = lc_plan(c->head, c->W, kept_seq != nullptr);
-    if (p.bytes > c->lc_cap) {
-        // sized for this log, doubling, never beyond a full one
-        const size_t full = lc_plan(c->log_cap, c->W_cap, true).bytes;
-        const size_t want = std::max(p.bytes, std::min(2 * c->lc_cap, full));
-        HIPCHK(c, stream_wait(c));
-        void *m = nullptr;
-        const hipError_t e = hipMalloc(&m, want);
-        if (e != hipSuccess)
-            return fail(c, FB_ENOMEM, "hipMalloc(compaction scratch %zu B) failed: %s", want, hipGetErrorString(e));
-        if (c->lc_mem) hipFree(c->lc_mem);
-        c->lc_mem = m;
-        c->lc_cap = want;
-    }
-    char *const base = (char *)c->lc_mem;
-    LcArgs a{};
-    a.log = c->log_slot;
-    a.head = c->head;
-    a.W = c->W;
-    a.nt = p.nt;
-    a.live_chk = c->life.stale ? 1 : 0;
-    a.reg = c->reg;
-    a.epoch = c->epoch;
-    a.bitmap = (unsigned long long *)(base + p.bitmap);
-    a.wrel = (uint32_t *)(base + p.wrel);
-    a.tcnt = (uint32_t *)(base + p.tcnt);
-    a.tpre = (uint32_t *)(base + p.tpre);
-    a.dst = (int32_t *)(base + p.dst);
-    a.kept = kept_seq ? (int64_t *)(base + p.kept) : nullptr;
-    if (p.flag_grid > 0) {
-        Timer t(c, "lc_flag");
-        launch_lc_flag(a, t.st());
-    }
-    {
-        Timer t(c, "lc_scan");
-        launch_lc_scan(a, t.st());
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, stream_wait(c));
-    uint32_t live = 0;
-    HIPCHK(c, hipMemcpy(&live, a.tpre + p.nt, 4, hipMemcpyDeviceToHost));
-    if ((int64_t)live > c->head)
-        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (log head)", live, (long long)c->head);
-    if (expect_kept >= 0 && expect_kept != (int64_t)live)
-        return fail(c, FB_ESTATE, "the log holds %u live entries, the caller expected %lld", live, (long long)expect_kept);
-    if (kept_seq && cap < (int64_t)live)
-        return fail(c, FB_EINVAL, "kept_seq holds %lld entries, the log %u live ones", (long long)cap, live);
-    if (p.move.grid() > 0) {
-        Timer t(c, "lc_move");
-        launch_lc_move(a, t.st());
-    }
-    if (live) {
-        Timer t(c, "lc_copy");
-        launch_copy_words((uint32_t *)c->log_slot, (const uint32_t *)a.dst, (int64_t)live, t.st());
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, stream_wait(c));
-    if (kept_seq && live) HIPCHK(c, hipMemcpy(kept_seq, a.kept, (size_t)live * 8, hipMemcpyDeviceToHost));
-    c->head = (int64_t)live;
-    life_replaced(c->life);  // (with it the discarded FB_ENOSPC tick)
-    if (n_kept) *n_kept = (int64_t)live;
-    return FB_OK;
-}
-
-// A shard group's compaction, this rank's two halves.  The scratch is
-// fb_log_compact's allocation; `keep` bytes of it (a mark's local regions) survive a growth.
-static int lcs_scratch(fb_ctx *c, const LcsPlan &p, size_t keep) {
-    if (p.bytes <= c->lc_cap) return FB_OK;
-    // sized for this log, doubling, never beyond a full one
-    const size_t full = lcs_plan(std::max<int64_t>(c->head, (int64_t)c->log_cap * c->world), c->log_cap, c->W_cap, true).bytes;
-    const size_t want = std::max(p.bytes, std::min(2 * c->lc_cap, full));
+// The compactions' scratch, one allocation for fb_log_compact and a shard
+// group's two halves: sized for this log (`need` bytes), doubling, never beyond a full one
+// (`full`); `keep` bytes of it (a mark's local table) survive a growth.
+static int lc_scratch(fb_ctx *c, size_t need, size_t full, size_t keep) {
+    if (need <= c->lc_cap) return FB_OK;
+    const size_t want = std::max(need, std::min(2 * c->lc_cap, full));
     HIPCHK(c, stream_wait(c));
     void *m = nullptr;
     const hipError_t e = hipMalloc(&m, want);
@@ -1857,42 +1784,85 @@ static int lcs_scratch(fb_ctx *c, const LcsPlan &p, size_t keep) {
     return FB_OK;
 }
 
-static LcsArgs lcs_args(fb_ctx *c, const LcsPlan &p, bool want_kept) {
+// The kernels' arguments over the scratch as p lays it out.  A shard's global bitmap is the
+// caller's exchange buffer; on one GPU the log's index is its sequence, and the tables are one.
+static LcArgs lc_args(fb_ctx *c, const LcPlan &p, bool want_kept) {
     char *const base = (char *)c->lc_mem;
-    LcsArgs a{};
+    const auto table = [base](const LcTableAt &t, int nt) {
+        return LcTable{(unsigned long long *)(base + t.bits), (uint32_t *)(base + t.wrel), (uint32_t *)(base + t.tcnt),
+                       (uint32_t *)(base + t.tpre), nt};
+    };
+    LcArgs a{};
     a.log = c->log_slot;
-    a.lseq = c->lseq;
+    a.seq = c->shard ? c->lseq : nullptr;
     a.head = c->head;
-    a.head_local = c->head_local;
+    a.n = c->shard ? c->head_local : c->head;
     a.W = c->W;
-    a.ntl = p.ntl;
-    a.ntg = p.ntg;
+    a.slot_base = c->shard ? c->slot_base : 0;
     // (no sharded context commits lazily today: the test is kept for the day one does)
     a.live_chk = c->life.stale ? 1 : 0;
-    a.slot_base = c->slot_base;
     a.want_kept = want_kept ? 1 : 0;
     a.reg = c->reg;
     a.epoch = c->epoch;
-    a.lbitmap = (unsigned long long *)(base + p.lbitmap);
-    a.lwrel = (uint32_t *)(base + p.lwrel);
-    a.ltcnt = (uint32_t *)(base + p.ltcnt);
-    a.ltpre = (uint32_t *)(base + p.ltpre);
-    a.xbits = (unsigned long long *)c->lcs_buf;
-    a.gwrel = (uint32_t *)(base + p.gwrel);
-    a.gtcnt = (uint32_t *)(base + p.gtcnt);
-    a.gtpre = (uint32_t *)(base + p.gtpre);
+    a.loc = table(p.loc, p.ntl);
+    a.glob = table(p.glob, p.ntg);
+    if (c->shard) a.glob.bits = (unsigned long long *)c->lcs_buf;
     a.dst = (int32_t *)(base + p.dst);
-    a.dseq = (uint32_t *)(base + p.dseq);
+    a.dseq = c->shard ? (uint32_t *)(base + p.dseq) : nullptr;
     a.kept = want_kept ? (int64_t *)(base + p.kept) : nullptr;
     return a;
 }
-// k_lc_scan over a tile count array of the shard's scratch
-static LcArgs lcs_scan_args(int nt, uint32_t *tcnt, uint32_t *tpre) {
-    LcArgs s{};
-    s.nt = nt;
-    s.tcnt = tcnt;
-    s.tpre = tpre;
-    return s;
+
+// The log renumbered densely on the device (DESIGN.md §5d): count first
+// (k_lc_flag, k_lc_scan write only the scratch), synchronise, check, and only then move.
+int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t cap, int64_t *n_kept) {
+    if (!c) return FB_EINVAL;
+    if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
+    // (a discarded tick's results completed nothing: its clears are taken back before the count)
+    if (int rc_ = enter(c, Call::log_compact)) return rc_;
+    HIPCHK(c, hipSetDevice(c->device));
+    const LcPlan p = lc_plan(c->head, c->W, kept_seq != nullptr);
+    if (int rc_ = lc_scratch(c, p.bytes, lc_plan(c->log_cap, c->W_cap, true).bytes, 0)) return rc_;
+    const LcArgs a = lc_args(c, p, kept_seq != nullptr);
+    if (p.flag_grid > 0) {
+        Timer t(c, "lc_flag");
+        launch_lc_flag(a, false, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(a.loc, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t live = 0;
+    HIPCHK(c, hipMemcpy(&live, a.loc.tpre + p.ntl, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)live > c->head)
+        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (log head)", live, (long long)c->head);
+    if (expect_kept >= 0 && expect_kept != (int64_t)live)
+        return fail(c, FB_ESTATE, "the log holds %u live entries, the caller expected %lld", live, (long long)expect_kept);
+    if (kept_seq && cap < (int64_t)live)
+        return fail(c, FB_EINVAL, "kept_seq holds %lld entries, the log %u live ones", (long long)cap, live);
+    if (p.move.grid() > 0) {
+        Timer t(c, "lc_move");
+        launch_lc_move(a, false, t.st());
+    }
+    if (live) {
+        Timer t(c, "lc_copy");
+        launch_copy_words((uint32_t *)c->log_slot, (const uint32_t *)a.dst, (int64_t)live, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    if (kept_seq && live) HIPCHK(c, hipMemcpy(kept_seq, a.kept, (size_t)live * 8, hipMemcpyDeviceToHost));
+    c->head = (int64_t)live;
+    life_replaced(c->life);  // (with it the discarded FB_ENOSPC tick)
+    if (n_kept) *n_kept = (int64_t)live;
+    return FB_OK;
+}
+
+// A shard group's compaction, this rank's two halves.
+// (the scratch of a full log: lc_scratch's bound)
+static size_t lcs_full_bytes(const fb_ctx *c) {
+    return lcs_plan(std::max<int64_t>(c->head, (int64_t)c->log_cap * c->world), c->log_cap, c->W_cap, true).bytes;
 }
 
 int fb_log_compact_shard_bytes(fb_ctx *c, int64_t *bytes) {
@@ -1915,17 +1885,17 @@ int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int
     const Gate g = life_gate_log_compact_shard_mark(c->life, c->caps);
     if (int rc_ = enter(c, g)) return rc_;  // (an uncommitted tick's clears are taken back here)
     HIPCHK(c, hipSetDevice(c->device));
-    const LcsPlan p = lcs_plan(c->head, c->head_local, c->W, false);
-    if (int rc_ = lcs_scratch(c, p, 0)) return rc_;
+    const LcPlan p = lcs_plan(c->head, c->head_local, c->W, false);
+    if (int rc_ = lc_scratch(c, p.bytes, lcs_full_bytes(c), 0)) return rc_;
     c->lcs_buf = device_buffer;
-    const LcsArgs a = lcs_args(c, p, false);
+    const LcArgs a = lc_args(c, p, false);
     if (p.flag_grid > 0) {
         Timer t(c, "lcs_flag");
-        launch_lcs_flag(a, t.st());
+        launch_lc_flag(a, true, t.st());
     }
     {
         Timer t(c, "lc_scan");
-        launch_lc_scan(lcs_scan_args(p.ntl, a.ltcnt, a.ltpre), t.st());
+        launch_lc_scan(a.loc, t.st());
     }
     if (p.mark_grid > 0) {
         Timer t(c, "lcs_mark");
@@ -1934,7 +1904,7 @@ int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     uint32_t live = 0;
-    HIPCHK(c, hipMemcpy(&live, a.ltpre + p.ntl, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&live, a.loc.tpre + p.ntl, 4, hipMemcpyDeviceToHost));
     if ((int64_t)live > c->head_local)
         return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (the log shard's entries)", live,
                     (long long)c->head_local);
@@ -1956,21 +1926,21 @@ int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_s
         return fail(c, FB_ESTATE, "the log changed under a marked compaction");
     }
     const bool want_kept = kept_seq != nullptr;
-    const LcsPlan p = lcs_plan(c->head, c->head_local, c->W, want_kept);
-    if (int rc_ = lcs_scratch(c, p, p.keep)) return rc_;
-    const LcsArgs a = lcs_args(c, p, want_kept);
+    const LcPlan p = lcs_plan(c->head, c->head_local, c->W, want_kept);
+    if (int rc_ = lc_scratch(c, p.bytes, lcs_full_bytes(c), p.keep)) return rc_;
+    const LcArgs a = lc_args(c, p, want_kept);
     if (p.count_grid > 0) {
         Timer t(c, "lcs_count");
         launch_lcs_count(a, t.st());
     }
     {
         Timer t(c, "lc_scan");
-        launch_lc_scan(lcs_scan_args(p.ntg, a.gtcnt, a.gtpre), t.st());
+        launch_lc_scan(a.glob, t.st());
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     uint32_t total = 0;
-    HIPCHK(c, hipMemcpy(&total, a.gtpre + p.ntg, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&total, a.glob.tpre + p.ntg, 4, hipMemcpyDeviceToHost));
     if ((int64_t)total != n_live_global || n_live_global > c->head || n_live_global < c->lcs_live) {
         life_lcs_unmarked(c->life);
         return fail(c, FB_ESTATE, "the reduced bitmap holds %u live entries, the group agreed on %lld (this rank: %lld of %lld)",
@@ -1982,7 +1952,7 @@ int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_s
     const int64_t live = c->lcs_live;
     if (p.move.grid() > 0) {
         Timer t(c, "lcs_move");
-        launch_lcs_move(a, t.st());
+        launch_lc_move(a, true, t.st());
     }
     if (live) {
         Timer t(c, "lc_copy");

@@ -575,47 +575,40 @@ void launch_copy_multi(const CopyMulti &m, Stream st);
 // the dense orphan list from per-tile segments (dst may be host-mapped memory): the
 // segments concatenated in tile order (each is ascending already, so the list is)
 void launch_orph_gather(int64_t *dst, const int64_t *src, const uint32_t *cnt, int ntile, Stream st);
-// fb_log_compact (grids and the scratch regions: lc_plan, faasbal_layout.h).  Entry q of the
-// log is live iff log[q] >= 0 and (live_chk: entries of dead registrations may be in the
-// log) its slot holds a record and q >= epoch[slot] -- k_log_normalize's rule.
-struct LcArgs {
-    const int32_t *log;
-    int64_t head;
-    int W, nt, live_chk;
-    const uint8_t *reg;
-    uint32_t *epoch;             // read by the flag pass, remapped by the move pass
-    unsigned long long *bitmap;  // [nt * kLcWords] live bits
-    uint32_t *wrel;              // [nt * kLcWords] live entries of the tile before the word
-    uint32_t *tcnt, *tpre;       // [nt] live entries of a tile, [nt + 1] before it
-    int32_t *dst;                // [live] the survivors' slots in order
-    int64_t *kept;               // [live] their old sequences (null: not wanted)
+// Log compaction, one GPU and a shard group's (fb_log_compact; fb_log_compact_shard_mark /
+// _apply; grids and the scratch regions: lc_plan and lcs_plan, faasbal_layout.h).  Entry i of
+// the log (sequence seq[i], ascending; on one GPU the index is the sequence) is live iff
+// log[i] >= 0 and (live_chk: entries of dead registrations may be in the log) its slot holds a
+// record and its sequence is >= epoch[slot] -- k_log_normalize's rule.  A shard's entries name
+// global slots: slot_base is taken off.
+//
+// The rank table over a live bitmap of nt kLcTile-entry tiles: set bits below bit q =
+// tpre[q / kLcTile] + wrel[q / 64] + the set bits of word q / 64 below q.
+struct LcTable {
+    unsigned long long *bits;  // [nt * kLcWords] the bitmap
+    uint32_t *wrel;            // [nt * kLcWords] set bits of the word's tile before the word
+    uint32_t *tcnt, *tpre;     // [nt] set bits of a tile, [nt + 1] before it (tpre[nt]: all)
+    int nt;
 };
-void launch_lc_flag(const LcArgs &a, Stream st);
-void launch_lc_scan(const LcArgs &a, Stream st);
-void launch_lc_move(const LcArgs &a, Stream st);
-// fb_log_compact_shard_mark / _apply (grids and the scratch regions: lcs_plan,
-// faasbal_layout.h).  Local entry i (sequence lseq[i], ascending) is live by LcArgs' rule with
-// the shard's forms: the entry names a global slot (slot_base is taken off) and the epoch test
-// compares its sequence, not its index.
-struct LcsArgs {
-    const int32_t *log;          // [head_local] the shard's entries
-    const uint32_t *lseq;        // [head_local] their global sequences
-    int64_t head, head_local;
-    int W, ntl, ntg, live_chk, slot_base, want_kept;
+struct LcArgs {
+    const int32_t *log;          // [n] the entries
+    const uint32_t *seq;         // [n] their global sequences (null on one GPU)
+    int64_t head, n;             // sequences; entries (the shard's head_local; = head on one GPU)
+    int W, slot_base, live_chk, want_kept;
     const uint8_t *reg;
     uint32_t *epoch;             // read by the flag pass (live_chk), remapped by the move pass
-    unsigned long long *lbitmap; // [ntl * kLcWords] live bits by shard index
-    uint32_t *lwrel, *ltcnt, *ltpre;  // as LcArgs' wrel / tcnt / tpre, over the shard
-    unsigned long long *xbits;   // [ntg * kLcWords] the exchange bitmap by sequence (the caller's buffer)
-    uint32_t *gwrel, *gtcnt, *gtpre;  // ... over the reduced exchange bitmap
-    int32_t *dst;                // [live local] the shard's survivors' slots in order
-    uint32_t *dseq;              // [live local] their new sequences
+    LcTable loc;                 // over the entries' indices
+    LcTable glob;                // over the sequences: bits is the reduced exchange bitmap, the
+                                 // caller's buffer (on one GPU glob is loc)
+    int32_t *dst;                // [live local] the survivors' slots in order
+    uint32_t *dseq;              // [live local] their new sequences (a shard's)
     int64_t *kept;               // [live global] old sequence of each new one (want_kept)
 };
-void launch_lcs_flag(const LcsArgs &a, Stream st);
-void launch_lcs_mark(const LcsArgs &a, Stream st);
-void launch_lcs_count(const LcsArgs &a, Stream st);
-void launch_lcs_move(const LcsArgs &a, Stream st);
+void launch_lc_flag(const LcArgs &a, bool shard, Stream st);
+void launch_lc_scan(const LcTable &t, Stream st);
+void launch_lc_move(const LcArgs &a, bool shard, Stream st);
+void launch_lcs_mark(const LcArgs &a, Stream st);
+void launch_lcs_count(const LcArgs &a, Stream st);
 // fb_pool_stats (grids, the partial rows' columns and the scratch regions: ps_plan,
 // faasbal_layout.h).  A slot is expired iff it holds a record and (now - hb) > tte (hb_chk:
 // heartbeat contexts; the tick's test); a log entry is live by LcArgs' rule.

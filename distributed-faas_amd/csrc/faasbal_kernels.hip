@@ -5093,294 +5093,273 @@ __global__ __launch_bounds__(kBS) void k_copy_words(uint32_t *__restrict__ dst, 
 }
 
 // ------------------------------------------------------------ log compaction
-// fb_log_compact (layout: lc_plan, faasbal_layout.h).  A wave streams one tile: lane l reads
-// entry 64 j + l of the tile for word j, eight words' loads in flight (each a 256-byte wave
-// load), and a ballot per word is that word of the live bitmap.  The liveness gathers
-// (live_chk) are branch-free: index clamped to slot 0, masked afterwards.
+// fb_log_compact; fb_log_compact_shard_mark / _apply (the launches, lc_plan and lcs_plan:
+// faasbal_layout.h).  A wave streams one tile: lane l reads entry 64 j + l of the tile for word
+// j, kLcBatch words' loads in flight (each a 256-byte wave load), and a ballot per word is
+// that word of the live bitmap.
 constexpr int kLcBatch = 8;
 
-__global__ __launch_bounds__(kBS) void k_lc_flag(LcArgs a) {
-    const int tile = (int)blockIdx.x * kWaves + wave_id();
-    if (tile >= a.nt) return;  // (the whole wave)
-    const int lane = lane_id();
-    const int64_t q0 = (int64_t)tile * kLcTile + lane;
-    unsigned long long mine = 0;  // lane j < kLcWords: word j of the tile
-    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
-        int32_t s[kLcBatch];
-        bool live[kLcBatch];
+// What a tile walk reads of a log (LcArgs' and PsArgs' fields of these names).
+struct LcWalk {
+    const int32_t *log;
+    const uint32_t *seq;  // (kShard only)
+    int64_t n;            // entries
+    int W, slot_base;     // (slot_base: kShard only)
+    const uint8_t *reg;   // (reg, epoch: kChk only)
+    const uint32_t *epoch;
+};
+
+// The batch step of the walk, words [j0, j0 + kLcBatch) of the tile whose entry 0 is i0 - lane:
+// s[k] the lane's entry of word j0 + k (as logged; the entry at n - 1 past the end), sc[k] its
+// slot in the rank's table clamped into [0, W), live[k] whether it is live (false past the
+// end).  Every load is unconditional at a clamped index and masked afterwards; the gathers of
+// live_chk go out in one round, and also() between their issue and their use is where a caller
+// puts gathers of its own at sc[].  kChk is live_chk, a constant of the launch: the caller
+// branches on it once, outside its loop over the batches, so that each form of the walk is
+// straight-line code whose next batch of loads goes out under the current one's ballots.
+//
+// kShard: the entries name global slots (slot_base is taken off) and carry their sequences in
+// seq[]; the one-GPU instantiation reads neither.  Three things differ between the two, and
+// are meant to:
+//   - the sequence the epoch test compares is the entry's index on one GPU (the log is dense:
+//     the index is the sequence) and seq[i] on a shard;
+//   - the range test 0 <= slot - slot_base < W is a shard's only, and one of live_chk's terms:
+//     it masks the gathers, which read at the clamped slot.  On one GPU a logged slot is one of
+//     the context's; a shard's entries are the rank's own by construction, which the flag pass
+//     trusts where it gathers nothing.  (k_ps_log<true> counts per slot, so it adds the range
+//     test itself, and never takes the kChk form: no sharded context commits lazily, and
+//     PsArgs carries no seq for the day one does.)
+//   - the clamp is two-sided in both.  It only bounds a read: one GPU's was below only, which
+//     the sign test made enough for a sound log; the upper side costs a v_min.
+template <bool kShard, bool kChk, class Also>
+__device__ __forceinline__ void lc_batch(const LcWalk &w, int64_t i0, int j0, int32_t (&s)[kLcBatch],
+                                         int32_t (&sc)[kLcBatch], bool (&live)[kLcBatch], Also &&also) {
+    const int wlast = w.W > 0 ? w.W - 1 : 0;
 #pragma unroll
-        for (int k = 0; k < kLcBatch; ++k) {
-            const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-            s[k] = a.log[q < a.head ? q : a.head - 1];
-        }
-        if (a.live_chk) {
-            uint8_t r[kLcBatch];
-            uint32_t e[kLcBatch];
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int32_t sc = s[k] > 0 ? s[k] : 0;
-                r[k] = a.reg[sc];
-                e[k] = a.epoch[sc];
-            }
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-                live[k] = q < a.head && s[k] >= 0 && r[k] && (uint64_t)q >= (uint64_t)e[k];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) live[k] = q0 + (int64_t)(j0 + k) * 64 < a.head && s[k] >= 0;
-        }
-#pragma unroll
-        for (int k = 0; k < kLcBatch; ++k) {
-            const unsigned long long m = __ballot(live[k]);
-            if (lane == j0 + k) mine = m;
-        }
+    for (int k = 0; k < kLcBatch; ++k) {
+        const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+        s[k] = w.log[i < w.n ? i : w.n - 1];
     }
+    // (run beside the gather it feeds: all eight ahead of the gathers, k_lc_flag<true> takes ten
+    // registers more and loses two waves)
+    const auto clamp = [&](int k) {
+        const int32_t ls = kShard ? s[k] - w.slot_base : s[k];
+        sc[k] = ls < 0 ? 0 : (ls > wlast ? wlast : ls);
+    };
+    if (kChk) {
+        uint8_t r[kLcBatch];
+        uint32_t e[kLcBatch], q[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            clamp(k);
+            r[k] = w.reg[(uint32_t)sc[k]];  // (unsigned: the byte gather takes a 32-bit offset on a scalar base)
+            e[k] = w.epoch[sc[k]];
+            if (kShard) q[k] = w.seq[i < w.n ? i : w.n - 1];
+        }
+        also();
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            if (kShard) {
+                const bool own = (uint32_t)(s[k] - w.slot_base) < (uint32_t)w.W;  // 0 <= slot - slot_base < W
+                live[k] = i < w.n && s[k] >= 0 && own && r[k] && q[k] >= e[k];
+            } else {
+                live[k] = i < w.n && s[k] >= 0 && r[k] && (uint64_t)i >= (uint64_t)e[k];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) clamp(k);
+        also();
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) live[k] = i0 + (int64_t)(j0 + k) * 64 < w.n && s[k] >= 0;
+    }
+}
+
+// The table's last step for one tile, a wave: lane j < kLcWords holds word j of the tile (the
+// other lanes 0).  wrel and tcnt, and (kBits) the word itself.
+template <bool kBits>
+__device__ __forceinline__ void lc_table_tile(const LcTable &t, int tile, unsigned long long mine) {
+    const int lane = lane_id();
     const uint32_t cnt = (uint32_t)__popcll(mine);
     const uint32_t inc = wave_incl_scan_u32(cnt);
     if (lane < kLcWords) {
-        a.bitmap[(int64_t)tile * kLcWords + lane] = mine;
-        a.wrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
+        if (kBits) t.bits[(int64_t)tile * kLcWords + lane] = mine;
+        t.wrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
     }
-    if (lane == 63) a.tcnt[tile] = inc;
+    if (lane == 63) t.tcnt[tile] = inc;
 }
 
-// tpre[t] = live entries before tile t; tpre[nt] = all of them (one workgroup)
-__global__ __launch_bounds__(kBS) void k_lc_scan(LcArgs a) {
-    __shared__ uint32_t l4[kWaves];
-    uint32_t carry = 0;
-    for (int b = 0; b < a.nt; b += kBS) {
-        const int i = b + (int)threadIdx.x;
-        const uint32_t v = i < a.nt ? a.tcnt[i] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_excl_scan_u32(v, l4, tot);
-        if (i < a.nt) a.tpre[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) a.tpre[a.nt] = carry;
+// The rank query: set bits of the table's bitmap below bit q (q >= head: all of them).
+// lc_rank_in is the query proper, for a q known to be below the head.
+__device__ __forceinline__ uint32_t lc_rank_in(const LcTable &t, uint64_t q) {
+    const int64_t w = (int64_t)(q >> 6);
+    return t.tpre[q / kLcTile] + t.wrel[w] + (uint32_t)__popcll(t.bits[w] & ((1ull << (q & 63)) - 1ull));
+}
+__device__ __forceinline__ uint32_t lc_rank(const LcTable &t, int64_t head, uint64_t q) {
+    return q >= (uint64_t)head ? t.tpre[t.nt] : lc_rank_in(t, q);
 }
 
-// Tile workgroups: survivor q of word j goes to tpre[tile] + wrel[word] + its rank in the
-// word (mbcnt of the bitmap word: no atomics); out of place, fb_log_compact copies dst back.
-// Slot workgroups: epoch[s] = live entries below min(epoch[s], head), the same rank query.
-__global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
-    const LcMoveLayout lay = lc_move_layout(a.nt, a.W);
-    const int bid = (int)blockIdx.x;
-    if (bid >= lay.end(kLcMoveTiles)) {
-        const int s = lay.rel(kLcMoveSlots, bid) * kBS + (int)threadIdx.x;
-        if (s >= a.W) return;
-        const uint64_t e = a.epoch[s];
-        uint32_t r;
-        if (e >= (uint64_t)a.head) {
-            r = a.tpre[a.nt];
-        } else {
-            const int64_t w = (int64_t)(e >> 6);
-            r = a.tpre[e / kLcTile] + a.wrel[w] + (uint32_t)__popcll(a.bitmap[w] & ((1ull << (e & 63)) - 1ull));
-        }
-        a.epoch[s] = r;
-        return;
-    }
-    const int tile = bid * kWaves + wave_id();
-    if (tile >= a.nt) return;  // (the whole wave)
+// lane j < kLcWords: word j of the tile and the set bits before it
+__device__ __forceinline__ void lc_tile_words(const LcTable &t, int tile, unsigned long long &mine, uint32_t &pre) {
     const int lane = lane_id();
-    const int64_t q0 = (int64_t)tile * kLcTile + lane;
-    unsigned long long mine = 0;
-    uint32_t pre = 0;
+    mine = 0;
+    pre = 0;
     if (lane < kLcWords) {
-        mine = a.bitmap[(int64_t)tile * kLcWords + lane];
-        pre = a.tpre[tile] + a.wrel[(int64_t)tile * kLcWords + lane];
+        mine = t.bits[(int64_t)tile * kLcWords + lane];
+        pre = t.tpre[tile] + t.wrel[(int64_t)tile * kLcWords + lane];
     }
+}
+
+// The tile scatter, a wave: the tile streamed again, survivor i of word j goes to tpre[tile] +
+// wrel[word] + its rank in the word (mbcnt of the bitmap word: no atomics), out of place.  One
+// GPU: its index is its old sequence (kept).  A shard: the rank of its sequence in the global
+// table is its new one (dseq).
+template <bool kShard>
+__device__ __forceinline__ void lc_scatter_tile(const LcArgs &a, int tile) {
+    const int lane = lane_id();
+    const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine;
+    uint32_t pre;
+    lc_tile_words(a.loc, tile, mine, pre);
     for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
         int32_t s[kLcBatch];
+        uint32_t q[kLcBatch];
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
-            const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-            s[k] = a.log[q < a.head ? q : a.head - 1];
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            const int64_t ic = i < a.n ? i : a.n - 1;
+            s[k] = a.log[ic];
+            if (kShard) q[k] = a.seq[ic];
         }
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
             const unsigned long long m = __shfl(mine, j0 + k, 64);
             const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
-            if ((m >> lane) & 1ull) {  // (a set bit: q < head)
+            if ((m >> lane) & 1ull) {  // (a set bit: i < n)
                 const int64_t o = (int64_t)p + popc_lt(m);
                 a.dst[o] = s[k];
-                if (a.kept) a.kept[o] = q0 + (int64_t)(j0 + k) * 64;
+                if (kShard) {
+                    // (a sequence is below the head: fb_load_shard and the ticks see to it; clamped
+                    // so that a broken one cannot send the query outside the scratch -- which also
+                    // makes lc_rank's head test dead here: a divergent branch per survivor less)
+                    const uint64_t qc = (uint64_t)q[k] < (uint64_t)a.head ? q[k] : (uint64_t)a.head - 1;
+                    a.dseq[o] = lc_rank_in(a.glob, qc);
+                } else if (a.kept) {
+                    a.kept[o] = i0 + (int64_t)(j0 + k) * 64;
+                }
             }
         }
     }
 }
 
-// ------------------------------------------------------------ a shard group's log compaction
-// fb_log_compact_shard_mark / _apply (layout: lcs_plan, faasbal_layout.h).
-//
-// k_lcs_flag: k_lc_flag over the rank's shard.  Entry i of the shard names a global slot
-// (slot_base off; the gathers at the clamped local slot, masked afterwards) and carries its
-// sequence in lseq[i], which is what the epoch test compares.
-__global__ __launch_bounds__(kBS) void k_lcs_flag(LcsArgs a) {
-    const int tile = (int)blockIdx.x * kWaves + wave_id();
-    if (tile >= a.ntl) return;  // (the whole wave)
+// a tile's words of the live bitmap, a wave: lane j < kLcWords gets word j (the other lanes 0)
+template <bool kShard, bool kChk>
+__device__ __forceinline__ unsigned long long lc_flag_tile(const LcArgs &a, int tile) {
     const int lane = lane_id();
-    const int wlast = a.W > 0 ? a.W - 1 : 0;
-    const int64_t i0 = (int64_t)tile * kLcTile + lane;
-    unsigned long long mine = 0;  // lane j < kLcWords: word j of the tile
+    const LcWalk w{a.log, a.seq, a.n, a.W, a.slot_base, a.reg, a.epoch};
+    unsigned long long mine = 0;
+#pragma unroll
     for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
-        int32_t s[kLcBatch];
+        int32_t s[kLcBatch], sc[kLcBatch];
         bool live[kLcBatch];
-#pragma unroll
-        for (int k = 0; k < kLcBatch; ++k) {
-            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
-            s[k] = a.log[i < a.head_local ? i : a.head_local - 1];
-        }
-        if (a.live_chk) {
-            uint8_t r[kLcBatch];
-            uint32_t e[kLcBatch], q[kLcBatch];
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int64_t i = i0 + (int64_t)(j0 + k) * 64;
-                const int32_t ls = s[k] - a.slot_base;
-                const int32_t sc = ls < 0 ? 0 : (ls > wlast ? wlast : ls);
-                r[k] = a.reg[sc];
-                e[k] = a.epoch[sc];
-                q[k] = a.lseq[i < a.head_local ? i : a.head_local - 1];
-            }
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int64_t i = i0 + (int64_t)(j0 + k) * 64;
-                const int32_t ls = s[k] - a.slot_base;
-                live[k] = i < a.head_local && s[k] >= 0 && ls >= 0 && ls < a.W && r[k] && q[k] >= e[k];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) live[k] = i0 + (int64_t)(j0 + k) * 64 < a.head_local && s[k] >= 0;
-        }
+        lc_batch<kShard, kChk>(w, (int64_t)tile * kLcTile + lane, j0, s, sc, live, [] {});
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
             const unsigned long long m = __ballot(live[k]);
             if (lane == j0 + k) mine = m;
         }
+        // (the gathers' form a batch at a time: run together, the batches take twice the registers)
+        if (kChk) __builtin_amdgcn_sched_barrier(0);
     }
-    const uint32_t cnt = (uint32_t)__popcll(mine);
-    const uint32_t inc = wave_incl_scan_u32(cnt);
-    if (lane < kLcWords) {
-        a.lbitmap[(int64_t)tile * kLcWords + lane] = mine;
-        a.lwrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
+    return mine;
+}
+
+// the local table but for tpre
+template <bool kShard>
+__global__ __launch_bounds__(kBS) void k_lc_flag(LcArgs a) {
+    prefetch_args(a);
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.loc.nt) return;  // (the whole wave)
+    lc_table_tile<true>(a.loc, tile, a.live_chk ? lc_flag_tile<kShard, true>(a, tile) : lc_flag_tile<kShard, false>(a, tile));
+}
+
+// tpre[t] = set bits before tile t; tpre[nt] = all of them (one workgroup)
+__global__ __launch_bounds__(kBS) void k_lc_scan(LcTable t) {
+    __shared__ uint32_t l4[kWaves];
+    uint32_t carry = 0;
+    for (int b = 0; b < t.nt; b += kBS) {
+        const int i = b + (int)threadIdx.x;
+        const uint32_t v = i < t.nt ? t.tcnt[i] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan_u32(v, l4, tot);
+        if (i < t.nt) t.tpre[i] = carry + ex;
+        carry += tot;
     }
-    if (lane == 63) a.ltcnt[tile] = inc;
+    if (threadIdx.x == 0) t.tpre[t.nt] = carry;
 }
 
 // The rank's bits of the exchange bitmap, owner computes: a thread per word of 64 sequences.
 // The shard's sequences ascend, so the entries of a word are contiguous in the shard: a lower
-// bound into lseq finds the first, and at most 64 follow.  Every word is written (0 where the
+// bound into seq finds the first, and at most 64 follow.  Every word is written (0 where the
 // rank has no live entry, past the head included): no zero pass, no atomics, and the same
 // bytes every time.
-__global__ __launch_bounds__(kBS) void k_lcs_mark(LcsArgs a) {
+__global__ __launch_bounds__(kBS) void k_lcs_mark(LcArgs a) {
+    prefetch_args(a);
     const int64_t w = (int64_t)blockIdx.x * kBS + threadIdx.x;
-    if (w >= (int64_t)a.ntg * kLcWords) return;
+    if (w >= (int64_t)a.glob.nt * kLcWords) return;
     const int64_t q0 = w * 64, q1 = q0 + 64;
-    int64_t lo = 0, hi = a.head_local;
+    int64_t lo = 0, hi = a.n;
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a.lseq[mid] < q0) lo = mid + 1;
+        if ((int64_t)a.seq[mid] < q0) lo = mid + 1;
         else hi = mid;
     }
     unsigned long long bits = 0;
-    if (lo < a.head_local) {
+    if (lo < a.n) {
         // the live bits of shard indices [lo, lo + 64): two words of the local bitmap
-        // (ntl * kLcWords of them: lo < head_local is inside, the next may not be)
-        const int64_t lw = lo >> 6, nwl = (int64_t)a.ntl * kLcWords;
+        // (loc.nt * kLcWords of them: lo < n is inside, the next may not be)
+        const int64_t lw = lo >> 6, nwl = (int64_t)a.loc.nt * kLcWords;
         const int sh = (int)(lo & 63);
-        const unsigned long long b0 = a.lbitmap[lw], b1 = lw + 1 < nwl ? a.lbitmap[lw + 1] : 0ull;
+        const unsigned long long b0 = a.loc.bits[lw], b1 = lw + 1 < nwl ? a.loc.bits[lw + 1] : 0ull;
         const unsigned long long lv = sh ? (b0 >> sh) | (b1 << (64 - sh)) : b0;
 #pragma unroll 4
         for (int k = 0; k < 64; ++k) {
             const int64_t i = lo + k;
-            if (i >= a.head_local) break;
-            const int64_t q = (int64_t)a.lseq[i];
+            if (i >= a.n) break;
+            const int64_t q = (int64_t)a.seq[i];
             if (q >= q1 || q >= a.head) break;
             if ((lv >> k) & 1ull) bits |= 1ull << (q - q0);
         }
     }
-    a.xbits[w] = bits;
+    a.glob.bits[w] = bits;
 }
 
-#ifdef FB_LCS_MARK_ATOMIC
-// The other form of the mark, measured against k_lcs_mark and not kept as the default
-// (a diagnostic build: build_lib(defines=("FB_LCS_MARK_ATOMIC",))): a zero pass
-// over the exchange bitmap, then a wave per local tile ORs its live entries' bits in, the lanes
-// that hit one word combined first (one vector atomic per word and wave step).
-__global__ __launch_bounds__(kBS) void k_lcs_zero(LcsArgs a) {
-    const int64_t w = (int64_t)blockIdx.x * kBS + threadIdx.x;
-    if (w < (int64_t)a.ntg * kLcWords) a.xbits[w] = 0ull;
-}
-__global__ __launch_bounds__(kBS) void k_lcs_mark_atomic(LcsArgs a) {
+// the global table but for tpre, its bits (the reduced exchange bitmap) given
+__global__ __launch_bounds__(kBS) void k_lcs_count(LcArgs a) {
+    prefetch_args(a);
     const int tile = (int)blockIdx.x * kWaves + wave_id();
-    if (tile >= a.ntl) return;  // (the whole wave)
-    const int lane = lane_id();
-    const int64_t i0 = (int64_t)tile * kLcTile + lane;
-    const unsigned long long mine = lane < kLcWords ? a.lbitmap[(int64_t)tile * kLcWords + lane] : 0ull;
-    for (int j = 0; j < kLcWords; ++j) {
-        const unsigned long long m = __shfl(mine, j, 64);
-        if (!m) continue;  // (wave-uniform)
-        const int64_t i = i0 + (int64_t)j * 64;
-        const uint32_t q = a.lseq[i < a.head_local ? i : a.head_local - 1];
-        bool todo = ((m >> lane) & 1ull) && (int64_t)q < a.head;
-        const uint32_t w = q >> 6;
-        const unsigned long long bit = 1ull << (q & 63);
-        unsigned long long left = __ballot(todo);
-        while (left) {
-            const int lead = __ffsll((long long)left) - 1;
-            const uint32_t lw = (uint32_t)__shfl((int)w, lead, 64);
-            const bool same = todo && w == lw;
-            unsigned long long v = same ? bit : 0ull;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-            if (lane == lead) atomicOr(&a.xbits[lw], v);
-            todo = todo && !same;
-            left = __ballot(todo);
-        }
-    }
-}
-#endif
-
-// The reduced exchange bitmap counted: each word's set bits before it in its tile (gwrel), each
-// tile's (gtcnt) -- k_lc_flag's last step, the bitmap given.
-__global__ __launch_bounds__(kBS) void k_lcs_count(LcsArgs a) {
-    const int tile = (int)blockIdx.x * kWaves + wave_id();
-    if (tile >= a.ntg) return;  // (the whole wave)
-    const int lane = lane_id();
-    const unsigned long long mine = lane < kLcWords ? a.xbits[(int64_t)tile * kLcWords + lane] : 0ull;
-    const uint32_t cnt = (uint32_t)__popcll(mine);
-    const uint32_t inc = wave_incl_scan_u32(cnt);
-    if (lane < kLcWords) a.gwrel[(int64_t)tile * kLcWords + lane] = inc - cnt;
-    if (lane == 63) a.gtcnt[tile] = inc;
+    if (tile >= a.glob.nt) return;  // (the whole wave)
+    lc_table_tile<false>(a.glob, tile, lane_id() < kLcWords ? a.glob.bits[(int64_t)tile * kLcWords + lane_id()] : 0ull);
 }
 
-// set bits of the reduced bitmap below sequence q, q <= head (the rank query of k_lc_move)
-__device__ __forceinline__ uint32_t lcs_rank(const LcsArgs &a, uint64_t q) {
-    if (q >= (uint64_t)a.head) return a.gtpre[a.ntg];
-    const int64_t w = (int64_t)(q >> 6);
-    return a.gtpre[q / kLcTile] + a.gwrel[w] + (uint32_t)__popcll(a.xbits[w] & ((1ull << (q & 63)) - 1ull));
-}
-
-// Local tile workgroups: survivor i of the shard goes to ltpre[tile] + lwrel[word] + its rank in
-// the word, with the rank of its sequence in the reduced bitmap as its new sequence (out of
-// place: the apply copies dst and dseq back).  Slot workgroups: epoch[s] = that rank of
-// min(epoch[s], head).  Kept workgroups (want_kept): k_lc_move's kept scatter over the reduced
-// bitmap -- set bit q goes to kept[its rank].
-__global__ __launch_bounds__(kBS) void k_lcs_move(LcsArgs a) {
-    const LcsMoveLayout lay = lcs_move_layout(a.ntl, a.W, a.want_kept ? a.ntg : 0);
+// Tile workgroups: lc_scatter_tile over the entries; fb_log_compact[_shard_apply] copies dst
+// (and dseq) back.  Slot workgroups: epoch[s] = the rank of min(epoch[s], head) in the global
+// table.  Kept workgroups (a shard with want_kept; one GPU writes kept in its tile role): the
+// reduced bitmap expanded -- set bit q goes to kept[its rank].
+template <bool kShard>
+__global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
+    prefetch_args(a);
+    const LcMoveLayout lay = lc_move_layout(a.loc.nt, a.W, kShard && a.want_kept ? a.glob.nt : 0);
     const int bid = (int)blockIdx.x;
-    const int lane = lane_id();
-    if (bid >= lay.end(kLcsMoveSlots)) {
-        const int tile = lay.rel(kLcsMoveKept, bid) * kWaves + wave_id();
-        if (tile >= a.ntg) return;  // (the whole wave)
-        unsigned long long mine = 0;
-        uint32_t pre = 0;
-        if (lane < kLcWords) {
-            mine = a.xbits[(int64_t)tile * kLcWords + lane];
-            pre = a.gtpre[tile] + a.gwrel[(int64_t)tile * kLcWords + lane];
-        }
+    if (kShard && bid >= lay.end(kLcMoveSlots)) {
+        const int tile = lay.rel(kLcMoveKept, bid) * kWaves + wave_id();
+        if (tile >= a.glob.nt) return;  // (the whole wave)
+        const int lane = lane_id();
+        unsigned long long mine;
+        uint32_t pre;
+        lc_tile_words(a.glob, tile, mine, pre);
 #pragma unroll 4
         for (int j = 0; j < kLcWords; ++j) {
             const unsigned long long m = __shfl(mine, j, 64);
@@ -5390,45 +5369,15 @@ __global__ __launch_bounds__(kBS) void k_lcs_move(LcsArgs a) {
         }
         return;
     }
-    if (bid >= lay.end(kLcsMoveTiles)) {
-        const int s = lay.rel(kLcsMoveSlots, bid) * kBS + (int)threadIdx.x;
+    if (bid >= lay.end(kLcMoveTiles)) {
+        const int s = lay.rel(kLcMoveSlots, bid) * kBS + (int)threadIdx.x;
         if (s >= a.W) return;
-        a.epoch[s] = lcs_rank(a, a.epoch[s]);
+        a.epoch[s] = lc_rank(a.glob, a.head, a.epoch[s]);
         return;
     }
     const int tile = bid * kWaves + wave_id();
-    if (tile >= a.ntl) return;  // (the whole wave)
-    const int64_t i0 = (int64_t)tile * kLcTile + lane;
-    unsigned long long mine = 0;
-    uint32_t pre = 0;
-    if (lane < kLcWords) {
-        mine = a.lbitmap[(int64_t)tile * kLcWords + lane];
-        pre = a.ltpre[tile] + a.lwrel[(int64_t)tile * kLcWords + lane];
-    }
-    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
-        int32_t s[kLcBatch];
-        uint32_t q[kLcBatch];
-#pragma unroll
-        for (int k = 0; k < kLcBatch; ++k) {
-            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
-            const int64_t ic = i < a.head_local ? i : a.head_local - 1;
-            s[k] = a.log[ic];
-            q[k] = a.lseq[ic];
-        }
-#pragma unroll
-        for (int k = 0; k < kLcBatch; ++k) {
-            const unsigned long long m = __shfl(mine, j0 + k, 64);
-            const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
-            if ((m >> lane) & 1ull) {  // (a set bit: i < head_local)
-                const int64_t o = (int64_t)p + popc_lt(m);
-                // (a sequence is below the head: fb_load_shard and the ticks see to it; clamped
-                // so that a broken one cannot send the query outside the scratch)
-                const uint64_t qc = (uint64_t)q[k] < (uint64_t)a.head ? q[k] : (uint64_t)a.head - 1;
-                a.dst[o] = s[k];
-                a.dseq[o] = lcs_rank(a, qc);
-            }
-        }
-    }
+    if (tile >= a.loc.nt) return;  // (the whole wave)
+    lc_scatter_tile<kShard>(a, tile);
 }
 
 // ------------------------------------------------------------ pool summary
@@ -5617,66 +5566,49 @@ __global__ __launch_bounds__(kBS) void k_ps_slots(PsArgs a) {
     }
 }
 
-// A wave per tile as k_lc_flag; a live entry's slot is looked up in the expired bitmap
-// k_ps_slots wrote (hb_chk), the gathers branch-free at a clamped slot.  kShard: the log is
-// the rank's shard (head: its entries), whose entries name global slots; no sharded context
-// leaves completed entries in the log (live_chk is never set: its test compares an entry's
-// index, which a shard's entries do not carry).
+// A wave per tile, lc_batch's walk; a live entry's slot is looked up in the expired bitmap
+// k_ps_slots wrote (hb_chk), that gather in the round of the batch's own.  kShard: the log is
+// the rank's shard (head: its entries), whose entries name global slots; an entry counts only
+// on one of the rank's slots, and live_chk is never run (see lc_batch).
+template <bool kShard, bool kChk>
+__device__ __forceinline__ void ps_log_tile(const PsArgs &a, int tile, uint32_t &nl, uint32_t &nle) {
+    const int lane = lane_id();
+    const LcWalk w{a.log, nullptr, a.head, a.W, kShard ? a.slot_base : 0, a.reg, a.epoch};
+    // (the gathers' form a batch at a time, not unrolled: run together, the batches take a
+    // quarter more registers and a wave of occupancy)
+#pragma unroll kChk ? 1 : kLcWords / kLcBatch
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch], sc[kLcBatch];
+        bool live[kLcBatch];
+        uint32_t xw[kLcBatch];  // the 32-bit half of the expired bitmap word with the slot in it
+        lc_batch<kShard, kChk>(w, (int64_t)tile * kLcTile + lane, j0, s, sc, live, [&] {
+            if (a.hb_chk) {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) xw[k] = reinterpret_cast<const uint32_t *>(a.xbits)[(uint32_t)sc[k] >> 5];
+            } else {
+#pragma unroll
+                for (int k = 0; k < kLcBatch; ++k) xw[k] = 0;
+            }
+        });
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const bool own = !kShard || (uint32_t)(s[k] - a.slot_base) < (uint32_t)a.W;
+            const bool exp = (xw[k] >> (sc[k] & 31)) & 1u;
+            nl += (uint32_t)__popcll(__ballot(live[k] && own && !exp));
+            nle += (uint32_t)__popcll(__ballot(live[k] && own && exp));
+        }
+    }
+}
 template <bool kShard>
 __global__ __launch_bounds__(kBS) void k_ps_log(PsArgs a) {
     prefetch_args(a);
     __shared__ uint32_t wc[kWaves][kPsLCols];
     const int tile = (int)blockIdx.x * kWaves + wave_id();
     const int lane = lane_id();
-    const int wlast = a.W > 0 ? a.W - 1 : 0;
-    const int64_t q0 = (int64_t)tile * kLcTile + lane;
     uint32_t nl = 0, nle = 0;
     if (tile < a.nt) {  // (the whole wave)
-        for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
-            int32_t s[kLcBatch], sc[kLcBatch];
-            uint8_t r[kLcBatch];
-            uint32_t e[kLcBatch];
-            unsigned long long xw[kLcBatch];
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-                s[k] = a.log[q < a.head ? q : a.head - 1];
-            }
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                // (a completed entry, -1, stays negative: slot_base >= 0)
-                if (kShard) s[k] = s[k] < 0 ? s[k] : s[k] - a.slot_base;
-                sc[k] = s[k] < 0 ? 0 : (s[k] > wlast ? wlast : s[k]);
-            }
-            if (!kShard && a.live_chk) {
-#pragma unroll
-                for (int k = 0; k < kLcBatch; ++k) {
-                    r[k] = a.reg[sc[k]];
-                    e[k] = a.epoch[sc[k]];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < kLcBatch; ++k) {
-                    r[k] = 1;
-                    e[k] = 0;
-                }
-            }
-            if (a.hb_chk) {
-#pragma unroll
-                for (int k = 0; k < kLcBatch; ++k) xw[k] = a.xbits[sc[k] >> 6];
-            } else {
-#pragma unroll
-                for (int k = 0; k < kLcBatch; ++k) xw[k] = 0;
-            }
-#pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) {
-                const int64_t q = q0 + (int64_t)(j0 + k) * 64;
-                const bool live = q < a.head && s[k] >= 0 && (!kShard || s[k] < a.W) && r[k] && (uint64_t)q >= (uint64_t)e[k];
-                const bool exp = (xw[k] >> (sc[k] & 63)) & 1ull;
-                nl += (uint32_t)__popcll(__ballot(live && !exp));
-                nle += (uint32_t)__popcll(__ballot(live && exp));
-            }
-        }
+        if (!kShard && a.live_chk) ps_log_tile<kShard, true>(a, tile, nl, nle);
+        else ps_log_tile<kShard, false>(a, tile, nl, nle);
     }
     if (lane == 0) {
         wc[wave_id()][0] = nl;
@@ -5831,42 +5763,22 @@ void launch_log_normalize(int32_t *log, int64_t n, const uint8_t *reg, const uin
     const int grid = (int)std::min<int64_t>(cdiv(n, kBS), 8192);
     hipExtLaunchKernelGGL(k_log_normalize, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, log, n, reg, epoch);
 }
-void launch_lc_flag(const LcArgs &a, Stream st) {
-    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
-    if (p.flag_grid > 0) hipExtLaunchKernelGGL(k_lc_flag, dim3(p.flag_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+static LcPlan lc_plan_of(const LcArgs &a, bool shard) {
+    return shard ? lcs_plan(a.head, a.n, a.W, a.want_kept != 0) : lc_plan(a.head, a.W, a.want_kept != 0);
 }
-void launch_lc_scan(const LcArgs &a, Stream st) {
-    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
-    hipExtLaunchKernelGGL(k_lc_scan, dim3(p.scan_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+template <class K, class A>
+static void lc_launch(K k, int grid, const A &a, Stream st) {
+    if (grid > 0) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
 }
-void launch_lc_move(const LcArgs &a, Stream st) {
-    const LcPlan p = lc_plan(a.head, a.W, a.kept != nullptr);
-    if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lc_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+void launch_lc_flag(const LcArgs &a, bool shard, Stream st) {
+    lc_launch(shard ? k_lc_flag<true> : k_lc_flag<false>, lc_plan_of(a, shard).flag_grid, a, st);
 }
-void launch_lcs_flag(const LcsArgs &a, Stream st) {
-    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
-    if (p.flag_grid > 0) hipExtLaunchKernelGGL(k_lcs_flag, dim3(p.flag_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
+void launch_lc_scan(const LcTable &t, Stream st) { lc_launch(k_lc_scan, kLcScanGrid, t, st); }
+void launch_lc_move(const LcArgs &a, bool shard, Stream st) {
+    lc_launch(shard ? k_lc_move<true> : k_lc_move<false>, lc_plan_of(a, shard).move.grid(), a, st);
 }
-void launch_lcs_mark(const LcsArgs &a, Stream st) {
-    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
-#ifdef FB_LCS_MARK_ATOMIC
-    if (p.mark_grid > 0) {
-        hipExtLaunchKernelGGL(k_lcs_zero, dim3(p.mark_grid), dim3(kBS), 0, st.s, st.e0, p.flag_grid > 0 ? nullptr : st.e1, 0, a);
-        if (p.flag_grid > 0)
-            hipExtLaunchKernelGGL(k_lcs_mark_atomic, dim3(p.flag_grid), dim3(kBS), 0, st.s, nullptr, st.e1, 0, a);
-    }
-#else
-    if (p.mark_grid > 0) hipExtLaunchKernelGGL(k_lcs_mark, dim3(p.mark_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
-#endif
-}
-void launch_lcs_count(const LcsArgs &a, Stream st) {
-    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
-    if (p.count_grid > 0) hipExtLaunchKernelGGL(k_lcs_count, dim3(p.count_grid), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
-}
-void launch_lcs_move(const LcsArgs &a, Stream st) {
-    const LcsPlan p = lcs_plan(a.head, a.head_local, a.W, a.want_kept != 0);
-    if (p.move.grid() > 0) hipExtLaunchKernelGGL(k_lcs_move, dim3(p.move.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);
-}
+void launch_lcs_mark(const LcArgs &a, Stream st) { lc_launch(k_lcs_mark, lc_plan_of(a, true).mark_grid, a, st); }
+void launch_lcs_count(const LcArgs &a, Stream st) { lc_launch(k_lcs_count, lc_plan_of(a, true).count_grid, a, st); }
 void launch_ps_slots(const PsArgs &a, Stream st) {
     const PsPlan p = ps_plan(a.W, a.Qn, a.head);
     if (p.slots.grid() > 0) hipExtLaunchKernelGGL(k_ps_slots<false>, dim3(p.slots.grid()), dim3(kBS), 0, st.s, st.e0, st.e1, 0, a);

@@ -257,88 +257,93 @@ FB_HD CopyMultiLayout copy_multi_layout(const CopyMulti &m) {
 }
 
 // ---------------------------------------------------------------------------------------
-// fb_log_compact: three launches over the log's kLcTile-entry tiles, a wave per tile (four
-// per workgroup), and the scratch they share.
-//   k_lc_flag  a workgroup per four tiles: the live bitmap (kLcWords 64-bit words per tile,
-//              whole tiles: bits past the head are 0), each word's live count before it in
-//              its tile (wrel), each tile's live count (tcnt)
-//   k_lc_scan  one workgroup: tpre[t] = live entries before tile t, tpre[nt] = all of them
-//   k_lc_move  the tile workgroups scatter the survivors (dst, and kept: their old
-//              sequences), then a workgroup per kBS slots remaps the epochs
-// lc_plan states the grids, the counts and the scratch's regions (256-byte aligned byte
-// offsets) for a log of `head` entries and W slots; the launchers and the allocation both
-// read them from it (tests/lc_probe.cpp walks it on the CPU).
-constexpr int kLcTile = kFTile;
-constexpr int kLcWords = kLcTile / 64;
-enum { kLcMoveTiles, kLcMoveSlots };
-struct LcMoveLayout : Roles<2> {};
-FB_HD LcMoveLayout lc_move_layout(int nt, int W) { return {{{quarter(nt), (int)cdiv(W, kBS)}}}; }
-struct LcPlan {
-    int nt;      // tiles
-    int64_t nw;  // bitmap words
-    int flag_grid, scan_grid;
-    LcMoveLayout move;
-    size_t bitmap, wrel, tcnt, tpre, dst, kept;  // regions: nw x 8, nw x 4, nt x 4, (nt + 1) x 4, head x 4, head x 8 bytes
-    size_t bytes;
-};
-inline LcPlan lc_plan(int64_t head, int W, bool want_kept) {
-    LcPlan p{};
-    p.nt = (int)cdiv(head, kLcTile);
-    p.nw = (int64_t)p.nt * kLcWords;
-    p.flag_grid = quarter(p.nt);
-    p.scan_grid = 1;
-    p.move = lc_move_layout(p.nt, W);
+// A scratch allocation's regions, handed out front to back at 256-byte aligned byte offsets.
+struct Regions {
     size_t o = 0;
-    auto take = [&o](size_t b) {
+    size_t take(size_t b) {
         const size_t at = o;
         o += (b + 255) & ~(size_t)255;
         return at;
-    };
-    p.bitmap = take((size_t)p.nw * 8);
-    p.wrel = take((size_t)p.nw * 4);
-    p.tcnt = take((size_t)p.nt * 4);
-    p.tpre = take(((size_t)p.nt + 1) * 4);
-    p.dst = take((size_t)head * 4);
-    p.kept = take(want_kept ? (size_t)head * 8 : 0);
-    p.bytes = o;
-    return p;
-}
+    }
+};
 
 // ---------------------------------------------------------------------------------------
-// fb_log_compact_shard_mark / _apply: a rank's two halves of its group's compaction.  The
-// shard holds head_local entries (lseq: their global sequences, ascending) of the `head`
-// sequences; local tiles and words are over the shard's indices, global ones over sequences.
-//   mark:   k_lcs_flag   a workgroup per four local tiles: k_lc_flag's three outputs over the
-//                        shard (lbitmap, lwrel, ltcnt)
-//           k_lc_scan    ltpre over the local tiles; ltpre[ntl] = the rank's live count
-//           k_lcs_mark   a thread per global word: the rank's bits of the exchange bitmap
-//                        (the caller's buffer, nwg words, every one written)
-//   apply:  k_lcs_count  a workgroup per four global tiles of the reduced bitmap: gwrel, gtcnt
-//           k_lc_scan    gtpre; gtpre[ntg] = the group's live count
-//           k_lcs_move   the local tile workgroups scatter the shard's survivors (dst: slots,
-//                        dseq: new sequences), a workgroup per kBS slots remaps the epochs,
-//                        then (want_kept) the global tile workgroups expand the bitmap (kept)
-// The local regions come first: they are written by the mark and read by the apply, and stay
-// where they are (or are copied, `keep` bytes) when the apply grows the scratch for a kept list.
-enum { kLcsMoveTiles, kLcsMoveSlots, kLcsMoveKept };
-struct LcsMoveLayout : Roles<3> {};
-FB_HD LcsMoveLayout lcs_move_layout(int ntl, int W, int ntg_kept) {
-    return {{{quarter(ntl), (int)cdiv(W, kBS), quarter(ntg_kept)}}};
+// Log compaction: fb_log_compact on one GPU, fb_log_compact_shard_mark / _apply on a rank of a
+// shard group.  One kernel family over kLcTile-entry tiles, a wave per tile (four per
+// workgroup), around LcTable, the rank table over a live bitmap (faasbal_kernels.h):
+//   k_lc_flag<kShard>  a workgroup per four tiles of the entries: the local table's bitmap
+//                      (kLcWords 64-bit words per tile, whole tiles: bits past the last entry
+//                      are 0), wrel and tcnt
+//   k_lc_scan          one workgroup: a table's tpre from its tcnt
+//   k_lcs_mark         a thread per word of the exchange bitmap (the caller's buffer, nwg
+//                      words, every one written): the rank's live bits by sequence
+//   k_lcs_count        a workgroup per four tiles of the reduced exchange bitmap: the global
+//                      table's wrel and tcnt, the bits given
+//   k_lc_move<kShard>  the tile workgroups scatter the survivors (dst; one GPU: kept, their old
+//                      sequences; a shard: dseq, their new ones), a workgroup per kBS slots
+//                      remaps the epochs, then (a shard with want_kept) the global tile
+//                      workgroups expand the reduced bitmap (kept)
+// One GPU: flag, scan, move over one table of the log's indices, which are its sequences.
+// A shard of head_local entries (seq: their global sequences, ascending) of the `head`
+// sequences keeps two tables, the local over the shard's indices, the global over sequences:
+//   mark:   flag, scan (local: tpre[ntl] = the rank's live count), mark
+//   apply:  count, scan (global: tpre[ntg] = the group's live count), move
+// lc_plan and lcs_plan state the grids, the counts and the scratch's regions for the two; the
+// launchers and the allocation both read them from there (tests/lc_probe.cpp and
+// tests/lcs_probe.cpp walk them on the CPU).
+constexpr int kLcTile = kFTile;
+constexpr int kLcWords = kLcTile / 64;
+constexpr int kLcScanGrid = 1;
+enum { kLcMoveTiles, kLcMoveSlots, kLcMoveKept };
+struct LcMoveLayout : Roles<3> {};
+FB_HD LcMoveLayout lc_move_layout(int nt, int W, int ntg_kept) {
+    return {{{quarter(nt), (int)cdiv(W, kBS), quarter(ntg_kept)}}};
 }
-struct LcsPlan {
-    int ntl, ntg;      // local tiles (of shard indices), global tiles (of sequences)
+// LcTable's regions: nt * kLcWords x 8, nt * kLcWords x 4, nt x 4, (nt + 1) x 4 bytes.  The
+// shard's global table has no bits region (own_bits = false: `bits` is not an offset).
+struct LcTableAt {
+    size_t bits, wrel, tcnt, tpre;
+};
+inline LcTableAt lc_table_at(Regions &r, int nt, bool own_bits) {
+    const size_t nw = (size_t)nt * kLcWords;
+    LcTableAt t{};
+    if (own_bits) t.bits = r.take(nw * 8);
+    t.wrel = r.take(nw * 4);
+    t.tcnt = r.take((size_t)nt * 4);
+    t.tpre = r.take(((size_t)nt + 1) * 4);
+    return t;
+}
+// (one GPU: the tables are one, ntg = ntl and nwg = nwl; no mark, count, dseq, keep or
+// exchange.)  A shard's local table comes first: it is written by the mark and read by the
+// apply, and stays where it is (or is copied, `keep` bytes) when the apply grows the scratch
+// for a kept list.
+struct LcPlan {
+    int ntl, ntg;      // local tiles (of the entries' indices), global tiles (of sequences)
     int64_t nwl, nwg;  // local bitmap words, global (exchange) bitmap words
     int flag_grid, mark_grid, count_grid, scan_grid;
-    LcsMoveLayout move;
-    // regions: nwl x 8, nwl x 4, ntl x 4, (ntl + 1) x 4 | nwg x 4, ntg x 4, (ntg + 1) x 4,
-    // head_local x 4, head_local x 4, head x 8 bytes
-    size_t lbitmap, lwrel, ltcnt, ltpre, gwrel, gtcnt, gtpre, dst, dseq, kept;
+    LcMoveLayout move;
+    LcTableAt loc, glob;
+    size_t dst, dseq, kept;  // regions: entries x 4, entries x 4, head x 8 bytes
     size_t keep;       // the bytes a mark leaves for its apply: [0, keep)
     size_t bytes;
     int64_t xbytes;    // the exchange bitmap: nwg x 8 bytes
 };
-inline LcsPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept) {
-    LcsPlan p{};
+inline LcPlan lc_plan(int64_t head, int W, bool want_kept) {
+    LcPlan p{};
+    p.ntl = p.ntg = (int)cdiv(head, kLcTile);
+    p.nwl = p.nwg = (int64_t)p.ntl * kLcWords;
+    p.flag_grid = quarter(p.ntl);
+    p.scan_grid = kLcScanGrid;
+    p.move = lc_move_layout(p.ntl, W, 0);
+    Regions r;
+    p.loc = p.glob = lc_table_at(r, p.ntl, true);
+    p.dst = r.take((size_t)head * 4);
+    p.kept = r.take(want_kept ? (size_t)head * 8 : 0);
+    p.bytes = r.o;
+    return p;
+}
+inline LcPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept) {
+    LcPlan p{};
     p.ntl = (int)cdiv(head_local, kLcTile);
     p.ntg = (int)cdiv(head, kLcTile);
     p.nwl = (int64_t)p.ntl * kLcWords;
@@ -346,27 +351,17 @@ inline LcsPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept)
     p.flag_grid = quarter(p.ntl);
     p.mark_grid = (int)cdiv(p.nwg, kBS);
     p.count_grid = quarter(p.ntg);
-    p.scan_grid = 1;
-    p.move = lcs_move_layout(p.ntl, W, want_kept ? p.ntg : 0);
+    p.scan_grid = kLcScanGrid;
+    p.move = lc_move_layout(p.ntl, W, want_kept ? p.ntg : 0);
     p.xbytes = p.nwg * 8;
-    size_t o = 0;
-    auto take = [&o](size_t b) {
-        const size_t at = o;
-        o += (b + 255) & ~(size_t)255;
-        return at;
-    };
-    p.lbitmap = take((size_t)p.nwl * 8);
-    p.lwrel = take((size_t)p.nwl * 4);
-    p.ltcnt = take((size_t)p.ntl * 4);
-    p.ltpre = take(((size_t)p.ntl + 1) * 4);
-    p.keep = o;
-    p.gwrel = take((size_t)p.nwg * 4);
-    p.gtcnt = take((size_t)p.ntg * 4);
-    p.gtpre = take(((size_t)p.ntg + 1) * 4);
-    p.dst = take((size_t)head_local * 4);
-    p.dseq = take((size_t)head_local * 4);
-    p.kept = take(want_kept ? (size_t)head * 8 : 0);
-    p.bytes = o;
+    Regions r;
+    p.loc = lc_table_at(r, p.ntl, true);
+    p.keep = r.o;
+    p.glob = lc_table_at(r, p.ntg, false);
+    p.dst = r.take((size_t)head_local * 4);
+    p.dseq = r.take((size_t)head_local * 4);
+    p.kept = r.take(want_kept ? (size_t)head * 8 : 0);
+    p.bytes = r.o;
     return p;
 }
 
@@ -417,17 +412,12 @@ inline PsPlan ps_plan(int W, int64_t Qn, int64_t head) {
     p.slots = ps_slots_layout(W, Qn);
     p.log_grid = quarter(p.nt);
     p.fold_grid = 1;
-    size_t o = 0;
-    auto take = [&o](size_t b) {
-        const size_t at = o;
-        o += (b + 255) & ~(size_t)255;
-        return at;
-    };
-    p.xbits = take((size_t)(p.nxw > 0 ? p.nxw : 1) * 8);  // (word 0 is read, and masked, by a log without slots)
-    p.srow = take((size_t)p.slots.count(kPsSlotsSlots) * kPsCols * 8);
-    p.qrow = take((size_t)p.slots.count(kPsSlotsQueue) * kPsQCols * 8);
-    p.lrow = take((size_t)p.log_grid * kPsLCols * 8);
-    p.bytes = o;
+    Regions r;
+    p.xbits = r.take((size_t)(p.nxw > 0 ? p.nxw : 1) * 8);  // (word 0 is read, and masked, by a log without slots)
+    p.srow = r.take((size_t)p.slots.count(kPsSlotsSlots) * kPsCols * 8);
+    p.qrow = r.take((size_t)p.slots.count(kPsSlotsQueue) * kPsQCols * 8);
+    p.lrow = r.take((size_t)p.log_grid * kPsLCols * 8);
+    p.bytes = r.o;
     return p;
 }
 

@@ -9,7 +9,7 @@
 //   slots.cover              1: k_lc_move's slot workgroups (through role_at) gave every slot
 //                            exactly once
 //   words.cover              1: every bitmap word a tile's wave writes (tile * kLcWords + lane,
-//                            lane < kLcWords) is below nw, each once
+//                            lane < kLcWords) is below nwl, each once
 // Built by tests/test_log_compact_host.py; it makes no HIP runtime call.
 #include <cstdio>
 #include <iostream>
@@ -49,11 +49,11 @@ int main() {
         const LcPlan p = lc_plan(head, (int)W, want != 0);
         bool words = true;
         {
-            std::vector<unsigned char> seen((size_t)p.nw, 0);
-            for (int t = 0; t < p.nt; ++t)
+            std::vector<unsigned char> seen((size_t)p.nwl, 0);
+            for (int t = 0; t < p.ntl; ++t)
                 for (int l = 0; l < kLcWords; ++l) {
                     const int64_t w = (int64_t)t * kLcWords + l;
-                    words = words && w < p.nw && ++seen[(size_t)w] == 1;
+                    words = words && w < p.nwl && ++seen[(size_t)w] == 1;
                 }
             for (unsigned char c : seen) words = words && c == 1;
         }
@@ -81,10 +81,10 @@ int main() {
         std::printf("head=%lld W=%lld nt=%d nw=%lld tile=%d words_per_tile=%d flag_grid=%d scan_grid=%d move_grid=%d"
                     " move_tiles=%d move_slots=%d bitmap=%zu wrel=%zu tcnt=%zu tpre=%zu dst=%zu kept=%zu bytes=%zu"
                     " flag.cover=%d move.cover=%d slots.cover=%d words.cover=%d\n",
-                    head, W, p.nt, (long long)p.nw, kLcTile, kLcWords, p.flag_grid, p.scan_grid, p.move.grid(),
-                    p.move.count(kLcMoveTiles), p.move.count(kLcMoveSlots), p.bitmap, p.wrel, p.tcnt, p.tpre, p.dst,
-                    p.kept, p.bytes, (int)tiles_cover(p.flag_grid, p.nt, head),
-                    (int)(tile_wgs == p.move.count(kLcMoveTiles) && tiles_cover(tile_wgs, p.nt, head)), (int)slots,
+                    head, W, p.ntl, (long long)p.nwl, kLcTile, kLcWords, p.flag_grid, p.scan_grid, p.move.grid(),
+                    p.move.count(kLcMoveTiles), p.move.count(kLcMoveSlots), p.loc.bits, p.loc.wrel, p.loc.tcnt, p.loc.tpre, p.dst,
+                    p.kept, p.bytes, (int)tiles_cover(p.flag_grid, p.ntl, head),
+                    (int)(tile_wgs == p.move.count(kLcMoveTiles) && tiles_cover(tile_wgs, p.ntl, head)), (int)slots,
                     (int)words);
     }
     return 0;
