@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "faasbal_fill.h"
 #include "faasbal_layout.h"
 
 namespace fb {
@@ -2555,6 +2556,102 @@ __global__ __launch_bounds__(kBS) void k_xscan(TickArgs a) {
     STAMP(a, SO, 15);
 }
 
+// ------------------------------------------------------------ the fill level (faasbal_fill.h)
+// The device side of the water-filling closed form: the round table in wave registers --
+// lane i of chunk k holds round r = 64 k + i, NCH chunks -- and the tick's HostOut record.
+template <int NCH, typename T>
+__device__ __forceinline__ T chunk_pick(const T (&v)[NCH], int k) {
+    static_assert(NCH <= 3, "at most three chunks");
+    if constexpr (NCH == 1) return v[0];
+    else if constexpr (NCH == 2) return k == 1 ? v[1] : v[0];
+    else return k == 0 ? v[0] : (k == 1 ? v[1] : v[2]);
+}
+// round r's value (its low word) in every lane
+template <int NCH, typename T>
+__device__ __forceinline__ int round_at(const T (&v)[NCH], int r) {
+    return __builtin_amdgcn_readlane((int)chunk_pick<NCH>(v, r >> 6), r & 63);
+}
+// The scan every wave runs alike over the totals A(r): S(r) = sum of A over the rounds before
+// r, the demand, the fill level L (the rounds r < rlim with S(r + 1) <= N_eff), S(L) and the
+// table's row L.  cap = kCapOfTable: the capacity is the table's own sum (sum_r A(r) over
+// r < max c = sum of c).  A sharded tick scans otot beside it, the totals of this rank's own
+// workers: So(r) places a task in the rank's log as S(r) places it in the tick (the two
+// scans' DPP chains interleave).  ST: int32_t where the one chunk's S(r) is only ever used
+// as a log index.
+constexpr int64_t kCapOfTable = -1;
+template <int NCH, typename ST = int64_t>
+struct FillScan {
+    ST Sv[NCH], Sov[NCH];  // S(r); sharded: So(r)
+    FillDemand d;
+    int L;
+    int64_t S_L, A_at_L, oSL;  // S(L), A(L) as the table has it; sharded: So(L)
+};
+template <int NCH, typename ST, bool OWN>
+__device__ __forceinline__ FillScan<NCH, ST> fill_scan_series(const uint32_t (&totv)[NCH],
+                                                              const uint32_t (&otot)[NCH], int maxc, int R,
+                                                              int64_t cap, int64_t O, int64_t T, bool redist) {
+    FillScan<NCH, ST> f;
+    const int lane = lane_id(), rlim = maxc < R ? maxc : R;
+    int64_t S1v[NCH], carry = 0, ocarry = 0;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        const bool in = 64 * k + lane < rlim;
+        const uint32_t v = in ? totv[k] : 0u;
+        const uint32_t incl = wave_incl_scan_u32(v);
+        S1v[k] = carry + (int64_t)incl;       // S(r + 1)
+        f.Sv[k] = (ST)(S1v[k] - (int64_t)v);  // S(r)
+        carry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        if constexpr (OWN) {
+            const uint32_t ov = in ? otot[k] : 0u;
+            const uint32_t oincl = wave_incl_scan_u32(ov);
+            f.Sov[k] = (ST)(ocarry + (int64_t)oincl - (int64_t)ov);
+            ocarry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)oincl, 63);
+        }
+    }
+    f.d = fill_demand(maxc, R, cap == kCapOfTable ? carry : cap, O, T, redist);
+    f.L = 0;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) f.L += __popcll(__ballot(64 * k + lane < rlim && S1v[k] <= f.d.N_eff));
+    f.S_L = (int64_t)round_at<NCH>(f.Sv, f.L);
+    f.A_at_L = (int64_t)(uint32_t)round_at<NCH>(totv, f.L);
+    if constexpr (OWN) f.oSL = (int64_t)round_at<NCH>(f.Sov, f.L);
+    return f;
+}
+template <int NCH, typename ST = int64_t>
+__device__ __forceinline__ FillScan<NCH, ST> fill_scan(const uint32_t (&totv)[NCH], int maxc, int R, int64_t cap,
+                                                       int64_t O, int64_t T, bool redist) {
+    return fill_scan_series<NCH, ST, false>(totv, totv, maxc, R, cap, O, T, redist);  // (no own series)
+}
+template <int NCH, typename ST = int64_t>
+__device__ __forceinline__ FillScan<NCH, ST> fill_scan(const uint32_t (&totv)[NCH], const uint32_t (&otot)[NCH],
+                                                       int maxc, int R, int64_t cap, int64_t O, int64_t T,
+                                                       bool redist) {
+    return fill_scan_series<NCH, ST, true>(totv, otot, maxc, R, cap, O, T, redist);
+}
+// The tick's record for the host, by one thread.  A tick that ends with a status leaves the
+// lengths as the launch poisoned them: fb_tick_wait reads none of them before it reruns or
+// fails, and a rerun that wrote no length is then caught by check_lengths.
+__device__ __forceinline__ void fill_record(const TickArgs &a, const FillDemand &d, const FillVerdict &v, int maxc,
+                                            int L, int64_t O, int64_t nev) {
+    a.hout->O = O;
+    a.hout->n_evicted = nev;
+    a.hout->cap_total = d.cap;
+    a.hout->maxc = maxc;
+    a.hout->L = L;
+    a.hout->status = v.status;
+    a.hout->N_eff = v.status ? 0 : d.N_eff;
+    a.hout->p = v.p;
+    a.hout->AL = v.AL;
+    if (!v.status && v.AL == 0) a.hout->new_qlen = 0;  // every worker saturated: nobody has rank p
+}
+// ... of a sharded tick: this rank's orphans, and oSL = So(L), its own log's share of S(L)
+__device__ __forceinline__ void fill_record(const TickArgs &a, const FillDemand &d, const FillVerdict &v, int maxc,
+                                            int L, int64_t O, int64_t nev, int64_t O_local, int64_t oSL) {
+    fill_record(a, d, v, maxc, L, O, nev);
+    a.hout->O_local = O_local;
+    if (!v.status && v.AL == 0) a.hout->n_local = oSL;  // all own capacity used
+}
+
 // ------------------------------------------------------------ k_plan2 (large grids, R <= 128)
 // k_plan for k_emit2 when k_scan's queue blocks also added their counts into
 // group rows (<= 64 groups of 2^gshift blocks): one workgroup per group reads
@@ -2644,12 +2741,10 @@ __global__ __launch_bounds__(kBS) void k_plan2(TickArgs a) {
     const int64_t O = (int64_t)red[0][0] + red[1][0] + red[2][0] + red[3][0];
     const int64_t nev = (int64_t)red[0][1] + red[1][1] + red[2][1] + red[3][1];
     const int maxc = (int)max(max(red[0][3], red[1][3]), max(red[2][3], red[3][3]));
-    const int rlim = maxc < R ? maxc : R;
     if (w == 0) {
         // per round r (lane i of chunk k: r = 64 k + i): A(r), the earlier groups' prefix,
-        // S(r) and the fill level L -- k_emit2's computation
+        // and the fill level L as k_emit2 finds it
         const int P = kBS / R;
-        int64_t carry = 0, S1v[2];
         uint32_t Av[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -2662,18 +2757,10 @@ __global__ __launch_bounds__(kBS) void k_plan2(TickArgs a) {
                 }
             if (r < R) gp_r[r] = sp;
             Av[k] = st_;
-            const uint32_t v = r < rlim ? st_ : 0u;
-            const uint32_t incl = wave_incl_scan_u32(v);
-            S1v[k] = carry + (int64_t)incl;
-            carry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         }
-        const int64_t cap = maxc > R ? INT64_MAX : carry;
-        const int64_t N = (a.redist ? O : 0) + a.T;
-        const int64_t N_eff = N < cap ? N : cap;
-        int L = 0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) L += __popcll(__ballot(64 * k + lane < rlim && S1v[k] <= N_eff));
-        if (lane == 0) nr_s = min(L + 2, R);
+        const FillScan<2> f = fill_scan<2>(Av, maxc, R, kCapOfTable, O, a.T, a.redist);
+        const int rlim = f.d.rlim;
+        if (lane == 0) nr_s = min(f.L + 2, R);
         if (g == 0 || a.repl) {
             int64_t *Ad = a.repl ? a.A_rep + (size_t)g * kRFused : a.A;
             DevTotals *Pd = a.repl ? a.P_rep + g : a.P;
@@ -2684,7 +2771,7 @@ __global__ __launch_bounds__(kBS) void k_plan2(TickArgs a) {
                 Pd->O = O;
                 Pd->O_local = O;
                 Pd->n_evicted = nev;
-                Pd->cap_total = cap;
+                Pd->cap_total = f.d.cap;
                 Pd->maxc = maxc;
             }
         }
@@ -2801,68 +2888,45 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
         int32_t raw = INT32_MIN;
         double hbp = 0.0;
         int s = -1;
-        int64_t O, nev = 0, cap;
-        int maxc, bm;
-        int rlim;
+        // ---- totals and the scanned round table from k_plan
+        if (pos < a.Qlog) {
+            raw = a.c_arr[pos];
+            hbp = a.c_hb[pos];
+            s = lq_slot(a, pos);
+        }
+        const int bm = a.qbm_raw[b];
+        const int64_t O = a.P->O, nev = a.P->n_evicted;
+        const int maxc = a.P->maxc;
+        const FillDemand d = fill_demand(maxc, a.R, a.P->cap_total, O, a.T, a.redist);
+        const int rlim = d.rlim;
         int L = 0;
-        int64_t S_L = 0, N_eff;
-        {
-            // ---- totals and the scanned round table from k_plan
-            if (pos < a.Qlog) {
-                raw = a.c_arr[pos];
-                hbp = a.c_hb[pos];
-                s = lq_slot(a, pos);
-            }
-            bm = a.qbm_raw[b];
-            O = a.P->O;
-            nev = a.P->n_evicted;
-            cap = a.P->cap_total;
-            maxc = a.P->maxc;
-            rlim = maxc < a.R ? maxc : a.R;
-            if (maxc > a.R) cap = INT64_MAX;
-            const int64_t N = (a.redist ? O : 0) + a.T;  // purge-only ticks report orphans, dispatch none
-            N_eff = N < cap ? N : cap;
-            int64_t carry = 0;  // S(rc)
-            for (int rc = 0; rc < rlim; rc += kBS) {
-                const int r = rc + threadIdx.x;
-                const unsigned long long v = r < rlim ? (unsigned long long)a.A[r] : 0ull;
-                unsigned long long tot;
-                const unsigned long long ex = block_excl_scan<unsigned long long>(v, red64, tot);
-                const int64_t S1 = carry + (int64_t)(ex + v);  // S(r + 1)
-                const bool ok = r < rlim && S1 <= N_eff;
-                const int k_w = __popcll(__ballot(ok));
-                if (lane == 0) misc[w] = k_w;
-                S_l[threadIdx.x + 1] = S1;
-                if (threadIdx.x == 0) S_l[0] = carry;
-                lds_barrier();
-                const int k = misc[0] + misc[1] + misc[2] + misc[3];
-                L += k;
-                S_L = S_l[k];
-                lds_barrier();
-                if (k < kBS) break;
-                carry += (int64_t)tot;
-            }
+        int64_t S_L = 0;
+        int64_t carry = 0;  // S(rc)
+        for (int rc = 0; rc < rlim; rc += kBS) {
+            const int r = rc + threadIdx.x;
+            const unsigned long long v = r < rlim ? (unsigned long long)a.A[r] : 0ull;
+            unsigned long long tot;
+            const unsigned long long ex = block_excl_scan<unsigned long long>(v, red64, tot);
+            const int64_t S1 = carry + (int64_t)(ex + v);  // S(r + 1)
+            const bool ok = r < rlim && S1 <= d.N_eff;
+            const int k_w = __popcll(__ballot(ok));
+            if (lane == 0) misc[w] = k_w;
+            S_l[threadIdx.x + 1] = S1;
+            if (threadIdx.x == 0) S_l[0] = carry;
+            lds_barrier();
+            const int k = misc[0] + misc[1] + misc[2] + misc[3];
+            L += k;
+            S_L = S_l[k];
+            lds_barrier();
+            if (k < kBS) break;
+            carry += (int64_t)tot;
         }
-        int status = 0;
-        if (maxc > a.R && L >= a.R - 1) status = 1;   // rows beyond the table needed: rerun wider
-        else if (a.head_in + N_eff > a.log_cap) status = 2;  // never write past the in-flight log (N_eff exact once R is)
-        const int64_t p = N_eff - S_L;
-        auto getA = [&](int r) -> int64_t { return r < rlim ? a.A[r] : (int64_t)0; };
-        const int64_t AL = (L < maxc && L < rlim) ? getA(L) : 0;
+        const FillVerdict vd =
+            fill_verdict(maxc, a.R, rlim, L, S_L, L < rlim ? a.A[L] : (int64_t)0, d.N_eff, a.head_in, a.log_cap);
+        const int64_t p = vd.p, AL = vd.AL;
         STAMP(a, SO, 2);
-        if (b == 0 && threadIdx.x == 0) {
-            a.hout->O = O;
-            a.hout->n_evicted = nev;
-            a.hout->cap_total = cap;
-            a.hout->maxc = maxc;
-            a.hout->L = L;
-            a.hout->status = status;
-            a.hout->N_eff = status ? 0 : N_eff;
-            a.hout->p = p;
-            a.hout->AL = AL;
-            if (AL == 0) a.hout->new_qlen = 0;
-        }
-        if (status) return;
+        if (b == 0 && threadIdx.x == 0) fill_record(a, d, vd, maxc, L, O, nev);
+        if (vd.status) return;
         // ---- water-filling emission, 256 rounds per chunk, rounds 0 .. L+1
         const int c = raw != INT32_MIN ? (a.deque ? raw : (raw > 1 ? raw : 1)) : 0;
         if (a.rb_slot && pos < a.Qlog) compact_out(a, pos, s, c, L);
@@ -2955,17 +3019,11 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
         }
         STAMP(a, SO, 4);
         if (c > 0) {
-            int64_t n_q = c < L ? c : L;
-            if (c > L && rankL < p) n_q += 1;
-            int64_t np = -1;
-            if (c > L) {
-                if (rankL >= p) np = rankL - p;
-                else if (c > L + 1) np = (AL - p) + exL1;
-                // the one position of rank p in A_L knows the next queue's length
-                if (rankL == p) a.hout->new_qlen = (AL - p) + exL1;
-            }
+            const FillNext nx = fill_next(c, L, rankL, p, AL, exL1);
+            const int64_t n_q = nx.n_q, np = nx.np;
+            if (nx.sets_qlen) a.hout->new_qlen = nx.qlen;
             if (a.deque) {
-                deque_finish(a, pos, s, c, L, n_q, c > L && rankL < p, np);
+                deque_finish(a, pos, s, c, L, n_q, nx.takes_L, np);
                 STAMP(a, SO, 15);
                 return;
             }
@@ -3018,14 +3076,6 @@ __global__ __launch_bounds__(kBS) void k_emit(TickArgs a_) {
 // i) from the round prefix plus the earlier segments' counts that k_scan stored
 // per 64-position segment, and the emission.  F / W roles as k_emit's.
 // NCH: 64-round chunks kept per lane (rounds 0 .. L+1): 1 for R = 32, 3 up to R = 128.
-
-template <int NCH, typename T>
-__device__ __forceinline__ T chunk_pick(const T (&v)[NCH], int k) {
-    T x = v[0];
-#pragma unroll
-    for (int i = 1; i < NCH; ++i) x = k == i ? v[i] : x;
-    return x;
-}
 
 // Log workgroup of a fused one-GPU tick (f_emit): orphan flags and their compaction.
 // The slot purge (k_scan's W role or the apply launch) wrote the died-registration
@@ -3191,50 +3241,14 @@ __device__ __forceinline__ void emit2_rounds(const TickArgs &a, int SO, int b, i
                                              int64_t cap) {
     const int lane = lane_id();
     const int R = a.R;
-    const int rlim = maxc < R ? maxc : R;
-    // ---- per wave: S(r) (lane i of chunk k: round 64 k + i), capacity, fill level L
-    int64_t Sv[NCH], S1v[NCH];
-    {
-        int64_t carry = 0;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            const int r = 64 * k + lane;
-            const uint32_t v = r < rlim ? totv[k] : 0u;
-            const uint32_t incl = wave_incl_scan_u32(v);
-            S1v[k] = carry + (int64_t)incl;  // S(r + 1)
-            Sv[k] = S1v[k] - (int64_t)v;     // S(r)
-            carry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        // fused: sum_r A(r) over r < max c = sum of c (PLAN: k_plan's capacity)
-        if constexpr (!PLAN) cap = carry;
-    }
-    if (maxc > R) cap = INT64_MAX;  // capacity beyond the table: only S(R) is known
-    const int64_t N = (a.redist ? O : 0) + a.T;  // purge-only ticks report orphans, dispatch none
-    const int64_t N_eff = N < cap ? N : cap;
-    int L = 0;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) L += __popcll(__ballot(64 * k + lane < rlim && S1v[k] <= N_eff));
-    const int Lc = L >> 6, Ll = L & 63;
-    const int64_t S_L = (int64_t)__builtin_amdgcn_readlane((int)chunk_pick<NCH>(Sv, Lc), Ll);
-    int status = 0;
-    if (maxc > R && L >= R - 1) status = 1;   // rows beyond the table needed: rerun wider
-    else if (a.head_in + N_eff > a.log_cap) status = 2;  // never write past the in-flight log (N_eff exact once R is)
-    const int64_t pL = N_eff - S_L;
-    const int64_t AL =
-        (L < maxc && L < rlim) ? (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)chunk_pick<NCH>(totv, Lc), Ll) : 0;
-    if (b == 0 && threadIdx.x == 0) {
-        a.hout->O = O;
-        a.hout->n_evicted = nev;
-        a.hout->cap_total = cap;
-        a.hout->maxc = maxc;
-        a.hout->L = L;
-        a.hout->status = status;
-        a.hout->N_eff = status ? 0 : N_eff;
-        a.hout->p = pL;
-        a.hout->AL = AL;
-        if (AL == 0) a.hout->new_qlen = 0;
-    }
-    if (status) return;
+    // ---- per wave: S(r), the capacity (PLAN: k_plan's, fused: the table's sum), fill level L
+    const FillScan<NCH> f = fill_scan<NCH>(totv, maxc, R, PLAN ? cap : kCapOfTable, O, a.T, a.redist);
+    const int rlim = f.d.rlim, L = f.L;
+    const int64_t S_L = f.S_L;
+    const FillVerdict vd = fill_verdict(maxc, R, rlim, L, S_L, f.A_at_L, f.d.N_eff, a.head_in, a.log_cap);
+    const int64_t pL = vd.p, AL = vd.AL;
+    if (b == 0 && threadIdx.x == 0) fill_record(a, f.d, vd, maxc, L, O, nev);
+    if (vd.status) return;
     // ---- rank base (in A_r) and task index base of this wave's segment, per round
     const int32_t raw = pos < a.Qlog ? raw0 : INT32_MIN;
     const int s = s0;
@@ -3246,32 +3260,23 @@ __device__ __forceinline__ void emit2_rounds(const TickArgs &a, int SO, int b, i
     for (int k = 0; k < NCH; ++k) {
         const int r = 64 * k + lane;
         rbv[k] = (int32_t)((r < rlim ? prev[k] : 0u) + segc[k]);
-        basev[k] = (int32_t)Sv[k] + rbv[k];  // valid for r <= rlim
+        basev[k] = (int32_t)f.Sv[k] + rbv[k];  // valid for r <= rlim
     }
     STAMP(a, SO, 2);
     int32_t *const out = a.log_slot + a.head_in;
     // ---- round L (partial: ranks < pL) and round L + 1 (ranks for the next queue)
-    const int L1 = L + 1, L1c = L1 >> 6, L1l = L1 & 63;
-    const int rbL = __builtin_amdgcn_readlane(chunk_pick<NCH>(rbv, Lc), Ll);
-    const int rbL1 = __builtin_amdgcn_readlane(chunk_pick<NCH>(rbv, L1c), L1l);
     const uint64_t mL = __ballot(c > L);
-    const int64_t rankL = (int64_t)rbL + popc_lt(mL);
-    const int64_t exL1 = (int64_t)rbL1 + popc_lt(__ballot(c > L1));
+    const int64_t rankL = (int64_t)round_at<NCH>(rbv, L) + popc_lt(mL);
+    const int64_t exL1 = (int64_t)round_at<NCH>(rbv, L + 1) + popc_lt(__ballot(c > L + 1));
     // round L's stores and the position's next state (free count, next queue)
     auto finish = [&]() {
         if (!(kDiagNow & 32) && c > L && rankL < pL) wt_store(out + S_L + rankL, s);
         if (c > 0) {
-            int64_t n_q = c < L ? c : L;
-            if (c > L && rankL < pL) n_q += 1;
-            int64_t np = -1;
-            if (c > L) {
-                if (rankL >= pL) np = rankL - pL;
-                else if (c > L1) np = (AL - pL) + exL1;
-                // the one position of rank pL in A_L knows the next queue's length
-                if (rankL == pL) a.hout->new_qlen = (AL - pL) + exL1;
-            }
+            const FillNext nx = fill_next(c, L, rankL, pL, AL, exL1);
+            const int64_t n_q = nx.n_q, np = nx.np;
+            if (nx.sets_qlen) a.hout->new_qlen = nx.qlen;
             if (a.deque) {
-                deque_finish(a, pos, s, c, L, n_q, c > L && rankL < pL, np);
+                deque_finish(a, pos, s, c, L, n_q, nx.takes_L, np);
                 return;
             }
             // the worker's next {free, queued}: one 8-byte store, only for the workers served
@@ -3939,6 +3944,19 @@ __global__ __launch_bounds__(kBS) void k_emit_win(TickArgs a) {
 // ------------------------------------------------------------ k_emit_shard
 __device__ __forceinline__ void shard_compact(const TickArgs &a, int bid);
 constexpr int kRCh = 3;  // 64-round chunks: rounds 0 .. L+1 <= 129
+// A sharded position's next state (c > 0; ls: its slot on this rank, -1 = another rank's):
+// the first position of round L left without a task knows both the next queue's and the own
+// log's length (n_local: the own tasks before it)
+__device__ __forceinline__ void shard_next(const TickArgs &a, const FillNext &nx, int s, int ls, int32_t raw,
+                                           int64_t n_local) {
+    if (nx.sets_qlen) {
+        a.hout->new_qlen = nx.qlen;
+        a.hout->n_local = n_local;
+    }
+    // the owned worker's next {free, queued} in one 8-byte store (the purge wrote {., 0})
+    if (ls >= 0) a.free_out[ls] = make_int2(raw - (int32_t)nx.n_q, nx.np >= 0 ? 1 : 0);
+    if (nx.np >= 0) a.queue_out[nx.np] = s;  // the next queue is replicated on every rank
+}
 // Phase 2 of a sharded tick.  Every rank computes the global water-filling from
 // the exchanged counts (identical on all ranks), writes the whole next LRU queue,
 // and appends only its own workers' tasks to its log shard -- in ascending global
@@ -3978,7 +3996,8 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
         const int cq = xc_get(a, pq);
         const int sq = lq_slot(a, pq);
         const int32_t rawq = a.c_arr[pq];
-        int64_t Av[kRCh], oAv[kRCh], pv[kRCh], opv[kRCh];
+        uint32_t Av[kRCh], oAv[kRCh];  // A(r) of all positions / of this rank's, lane i of chunk k: r = 64 k + i
+        int64_t pv[kRCh], opv[kRCh];
         int64_t O, cap;
         int maxc;
         uint32_t segc[kRCh] = {0, 0, 0}, osegc[kRCh] = {0, 0, 0};
@@ -4293,8 +4312,8 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
 #pragma unroll
             for (int k = 0; k < kRCh; ++k) {
                 const int r = min(64 * k + lane, R - 1);
-                Av[k] = a.A[r];
-                oAv[k] = a.oA[r];
+                Av[k] = (uint32_t)a.A[r];
+                oAv[k] = (uint32_t)a.oA[r];
                 pv[k] = a.qpre[(size_t)b * R + r];
                 opv[k] = a.opre[(size_t)b * R + r];
             }
@@ -4321,44 +4340,12 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
                     osegc[k] += in ? osv[k][q] : 0u;
                 }
         }
-        const int rlim = maxc < R ? maxc : R;
-        if (maxc > R) cap = INT64_MAX;
-        const int64_t N = (a.redist ? O : 0) + a.T;  // purge-only ticks report orphans, dispatch none
-        const int64_t N_eff = N < cap ? N : cap;
         // ---- per wave: S(r) and So(r) (lane i of chunk k: round 64 k + i), fill level L
-        int64_t Sv[kRCh], Sov[kRCh];
-        int L = 0;
-        {
-            int64_t carry = 0, ocarry = 0;
-#pragma unroll
-            for (int k = 0; k < kRCh; ++k) {
-                const int r = 64 * k + lane;
-                const uint32_t v = r < rlim ? (uint32_t)Av[k] : 0u;
-                const uint32_t ov = r < rlim ? (uint32_t)oAv[k] : 0u;
-                const uint32_t incl = wave_incl_scan_u32(v);
-                const uint32_t oincl = wave_incl_scan_u32(ov);
-                const int64_t S1 = carry + (int64_t)incl;  // S(r + 1)
-                Sv[k] = S1 - (int64_t)v;                   // S(r)
-                Sov[k] = ocarry + (int64_t)oincl - (int64_t)ov;
-                L += __popcll(__ballot(r < rlim && S1 <= N_eff));
-                carry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                ocarry += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)oincl, 63);
-            }
-        }
-        const int Lc = L >> 6, Ll = L & 63;
-        const int64_t S_L = (int64_t)__builtin_amdgcn_readlane((int)(Lc == 0 ? Sv[0] : (Lc == 1 ? Sv[1] : Sv[2])), Ll);
-        const int64_t oSL =
-            (int64_t)__builtin_amdgcn_readlane((int)(Lc == 0 ? Sov[0] : (Lc == 1 ? Sov[1] : Sov[2])), Ll);
-        // status 1 (the table is too narrow: every rank sees it, all relaunch) before
-        // status 2 (this rank's log shard is full), whose N_eff is exact only once the
-        // table is wide enough -- so the ranks never split between a relaunch and a failure
-        int status = 0;
-        if (maxc > R && L >= R - 1) status = 1;
-        else if (a.head_local + N_eff > a.log_cap) status = 2;
-        const int64_t p = N_eff - S_L;
-        // |A_L| from this wave's totals (lane L & 63 of chunk L >> 6)
-        const int64_t ALv = (int64_t)__builtin_amdgcn_readlane((int)(Lc == 0 ? Av[0] : (Lc == 1 ? Av[1] : Av[2])), Ll);
-        const int64_t AL = (L < maxc && L < rlim) ? ALv : 0;
+        const FillScan<kRCh> f = fill_scan<kRCh>(Av, oAv, maxc, R, cap, O, a.T, a.redist);
+        const int rlim = f.d.rlim, L = f.L;
+        const int64_t S_L = f.S_L, oSL = f.oSL;
+        const FillVerdict vd = fill_verdict(maxc, R, rlim, L, S_L, f.A_at_L, f.d.N_eff, a.head_local, a.log_cap);
+        const int64_t p = vd.p, AL = vd.AL;
         int64_t O_loc = 0, n_ev = 0;
         if (GRP && b == 0) {
             // this rank's orphans and evictions (its phase-1 tile counts) for the host
@@ -4376,24 +4363,10 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
             O_loc = (int64_t)sfo[0] + sfo[1] + sfo[2] + sfo[3];
             n_ev = (int64_t)sev[0] + sev[1] + sev[2] + sev[3];
         }
-        if (b == 0 && threadIdx.x == 0) {
-            a.hout->O = O;
-            a.hout->O_local = GRP ? O_loc : a.P->O_local;
-            a.hout->n_evicted = GRP ? n_ev : a.P->n_evicted;
-            a.hout->cap_total = cap;
-            a.hout->maxc = maxc;
-            a.hout->L = L;
-            a.hout->status = status;
-            a.hout->N_eff = status ? 0 : N_eff;
-            a.hout->p = p;
-            a.hout->AL = AL;
-            if (!status && AL == 0) {
-                a.hout->new_qlen = 0;
-                a.hout->n_local = oSL;  // every worker saturated: all own capacity used
-            }
-        }
+        if (b == 0 && threadIdx.x == 0)
+            fill_record(a, f.d, vd, maxc, L, O, GRP ? n_ev : a.P->n_evicted, GRP ? O_loc : a.P->O_local, oSL);
         STAMP(a, SO, 6);
-        if (status) return;
+        if (vd.status) return;
         const int c = pos < a.Qlog ? cq : 0;
         const int s = sq;
         const int ls = s >= 0 ? own_slot(a, s) : -1;
@@ -4406,8 +4379,8 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
             const int r = 64 * k + lane;
             rbv[k] = (int32_t)((r < rlim ? pv[k] : 0) + segc[k]);
             orbv[k] = (int32_t)((r < rlim ? opv[k] : 0) + osegc[k]);
-            basev[k] = (int32_t)Sv[k] + rbv[k];
-            obasev[k] = (int32_t)Sov[k] + orbv[k];
+            basev[k] = (int32_t)f.Sv[k] + rbv[k];
+            obasev[k] = (int32_t)f.Sov[k] + orbv[k];
         }
         int32_t *const lslot = a.log_slot + a.head_local;
         uint32_t *const lseq = a.lseq_out + a.head_local;
@@ -4458,38 +4431,18 @@ __global__ __launch_bounds__(kBS) void k_emit_shard(TickArgs a) {
             }
         }
         // ---- round L (partial: ranks < p) and round L + 1 (ranks for the next queue)
-        const int L1 = L + 1, L1c = L1 >> 6, L1l = L1 & 63;
-        const int rbL = __builtin_amdgcn_readlane(Lc == 0 ? rbv[0] : (Lc == 1 ? rbv[1] : rbv[2]), Ll);
-        const int orbL = __builtin_amdgcn_readlane(Lc == 0 ? orbv[0] : (Lc == 1 ? orbv[1] : orbv[2]), Ll);
-        const int rbL1 = __builtin_amdgcn_readlane(L1c == 0 ? rbv[0] : (L1c == 1 ? rbv[1] : rbv[2]), L1l);
         const uint64_t mL = __ballot(c > L);
         const uint64_t omL = __ballot(oc > L);
-        const int64_t rankL = (int64_t)rbL + popc_lt(mL);
-        const int64_t orankL = (int64_t)orbL + popc_lt(omL);
+        const int64_t rankL = (int64_t)round_at<kRCh>(rbv, L) + popc_lt(mL);
+        const int64_t orankL = (int64_t)round_at<kRCh>(orbv, L) + popc_lt(omL);
         if (oc > L && rankL < p) {
             const int64_t lp = oSL + orankL;
             lslot[lp] = s;
             lseq[lp] = hin + (uint32_t)(S_L + rankL);
         }
         if (aall && c > L && rankL < p) aall[S_L + rankL] = s;
-        const int64_t exL1 = (int64_t)rbL1 + popc_lt(__ballot(c > L1));
-        if (c > 0) {
-            int64_t n_q = c < L ? c : L;
-            if (c > L && rankL < p) n_q += 1;
-            int64_t np = -1;
-            if (c > L) {
-                if (rankL >= p) np = rankL - p;
-                else if (c > L1) np = (AL - p) + exL1;
-                if (rankL == p) {
-                    // first position of round L left without a task: both queue and own-log lengths
-                    a.hout->new_qlen = (AL - p) + exL1;
-                    a.hout->n_local = oSL + orankL;
-                }
-            }
-            // the owned worker's next {free, queued} in one 8-byte store (the purge wrote {., 0})
-            if (own) a.free_out[ls] = make_int2(rawq - (int32_t)n_q, np >= 0 ? 1 : 0);
-            if (np >= 0) a.queue_out[np] = s;  // the next queue is replicated on every rank
-        }
+        const int64_t exL1 = (int64_t)round_at<kRCh>(rbv, L + 1) + popc_lt(__ballot(c > L + 1));
+        if (c > 0) shard_next(a, fill_next(c, L, rankL, p, AL, exL1), s, ls, rawq, oSL + orankL);
         STAMP(a, SO, 15);
         return;
     }
@@ -4635,40 +4588,17 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_xp(TickArgs a) {
     // ---- the fill level (every wave alike; lane r = round r, one chunk)
     const int64_t O = (int64_t)xred[0][0] + xred[1][0] + xred[2][0] + xred[3][0];
     const int maxc = (int)max(max(xred[0][1], xred[1][1]), max(xred[2][1], xred[3][1]));
-    const int rlim = maxc < R ? maxc : R;
-    int64_t cap = (int64_t)wave_sum_u32(lane < R ? A0 : 0u);  // sum of c when max c <= R
-    if (maxc > R) cap = INT64_MAX;
-    const int64_t N = (a.redist ? O : 0) + a.T;
-    const int64_t N_eff = N < cap ? N : cap;
-    const uint32_t v = lane < rlim ? A0 : 0u, ov = lane < rlim ? oA0 : 0u;
-    const uint32_t incl = wave_incl_scan_u32(v), oincl = wave_incl_scan_u32(ov);
-    const int32_t Sv = (int32_t)(incl - v), Sov = (int32_t)(oincl - ov);  // S(r), So(r)
-    const int L = __popcll(__ballot(lane < rlim && (int64_t)incl <= N_eff));
-    const int64_t S_L = (int64_t)(uint32_t)__builtin_amdgcn_readlane(Sv, L);
-    const int64_t oSL = (int64_t)(uint32_t)__builtin_amdgcn_readlane(Sov, L);
-    int status = 0;
-    if (maxc > R && L >= R - 1) status = 1;
-    else if (a.head_local + N_eff > a.log_cap) status = 2;
-    const int64_t p = N_eff - S_L;
-    const int64_t AL = (L < maxc && L < rlim) ? (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)A0, L) : 0;
-    if (bid == 0 && t == 0) {
-        a.hout->O = O;
-        a.hout->O_local = O_loc;
-        a.hout->n_evicted = n_ev;
-        a.hout->cap_total = cap;
-        a.hout->maxc = maxc;
-        a.hout->L = L;
-        a.hout->status = status;
-        a.hout->N_eff = status ? 0 : N_eff;
-        a.hout->p = p;
-        a.hout->AL = AL;
-        if (!status && AL == 0) {
-            a.hout->new_qlen = 0;
-            a.hout->n_local = oSL;  // every worker saturated: all own capacity used
-        }
-    }
+    // (the capacity: the table's sum = sum of c when max c <= R)
+    const uint32_t Av[1] = {A0}, oAv[1] = {oA0};
+    const FillScan<1, int32_t> f = fill_scan<1, int32_t>(Av, oAv, maxc, R, kCapOfTable, O, a.T, a.redist);
+    const int rlim = f.d.rlim, L = f.L;
+    const int64_t S_L = f.S_L, oSL = f.oSL;
+    const int32_t Sv = f.Sv[0], Sov = f.Sov[0];  // S(r), So(r)
+    const FillVerdict vd = fill_verdict(maxc, R, rlim, L, S_L, f.A_at_L, f.d.N_eff, a.head_local, a.log_cap);
+    const int64_t p = vd.p, AL = vd.AL;
+    if (bid == 0 && t == 0) fill_record(a, f.d, vd, maxc, L, O, n_ev, O_loc, oSL);
     STAMP(a, SO, 6);
-    if (status) return;
+    if (vd.status) return;
     int32_t *const lslot = a.log_slot + a.head_local;
     uint32_t *const lseq = a.lseq_out + a.head_local;
     const uint32_t hin = (uint32_t)a.head_in;
@@ -4743,23 +4673,7 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_xp(TickArgs a) {
         }
         if (aall && c > L && rankL < p) aall[S_L + rankL] = s;
         const int64_t exL1 = (int64_t)rbL1 + popc_lt(__ballot(c > L1));
-        if (c > 0) {
-            int64_t n_q = c < L ? c : L;
-            if (c > L && rankL < p) n_q += 1;
-            int64_t np = -1;
-            if (c > L) {
-                if (rankL >= p) np = rankL - p;
-                else if (c > L1) np = (AL - p) + exL1;
-                if (rankL == p) {
-                    // first position of round L left without a task: both queue and own-log lengths
-                    a.hout->new_qlen = (AL - p) + exL1;
-                    a.hout->n_local = oSL + orankL;
-                }
-            }
-            // the owned worker's next {free, queued} in one 8-byte store (the purge wrote {., 0})
-            if (own) a.free_out[ls] = make_int2(rq[j] - (int32_t)n_q, np >= 0 ? 1 : 0);
-            if (np >= 0) a.queue_out[np] = s;  // the next queue is replicated on every rank
-        }
+        if (c > 0) shard_next(a, fill_next(c, L, rankL, p, AL, exL1), s, ls, rq[j], oSL + orankL);
     }
     STAMP(a, SO, 15);
 }
@@ -4842,12 +4756,10 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_wide(TickArgs a) {
     const int sq = lq_slot(a, pq);
     const int32_t rawq = a.c_arr[pq];
     const int64_t O = a.P->O;
-    int64_t cap = a.P->cap_total;
     const int maxc = a.P->maxc;
-    const int rlim = maxc < R ? maxc : R;
-    if (maxc > R) cap = INT64_MAX;
-    const int64_t N = (a.redist ? O : 0) + a.T;
-    const int64_t N_eff = N < cap ? N : cap;
+    const FillDemand d = fill_demand(maxc, R, a.P->cap_total, O, a.T, a.redist);
+    const int rlim = d.rlim;
+    const int64_t N_eff = d.N_eff;
     // ---- pass 1 (every wave alike): S(r), So(r) chunk by chunk until S(r + 1) > N_eff
     int L = 0;
     int64_t S_L = 0, oSL = 0;
@@ -4881,28 +4793,12 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_wide(TickArgs a) {
         }
     }
     lds_barrier();
-    int status = 0;  // (precedence as in k_emit_shard)
-    if (maxc > R && L >= R - 1) status = 1;  // R <= 64 * kWideMaxCh (the host caps it)
-    else if (a.head_local + N_eff > a.log_cap) status = 2;
-    const int64_t p = N_eff - S_L;
-    const int64_t AL = (L < maxc && L < rlim) ? a.A[L] : 0;
-    if (b == 0 && threadIdx.x == 0) {
-        a.hout->O = O;
-        a.hout->O_local = a.P->O_local;
-        a.hout->n_evicted = a.P->n_evicted;
-        a.hout->cap_total = cap;
-        a.hout->maxc = maxc;
-        a.hout->L = L;
-        a.hout->status = status;
-        a.hout->N_eff = status ? 0 : N_eff;
-        a.hout->p = p;
-        a.hout->AL = AL;
-        if (!status && AL == 0) {
-            a.hout->new_qlen = 0;
-            a.hout->n_local = oSL;
-        }
-    }
-    if (status) return;
+    // (R <= 64 * kWideMaxCh: the host caps it)
+    const FillVerdict vd =
+        fill_verdict(maxc, R, rlim, L, S_L, L < rlim ? a.A[L] : (int64_t)0, N_eff, a.head_local, a.log_cap);
+    const int64_t p = vd.p, AL = vd.AL;
+    if (b == 0 && threadIdx.x == 0) fill_record(a, d, vd, maxc, L, O, a.P->n_evicted, a.P->O_local, oSL);
+    if (vd.status) return;
     const int c = pos < a.Qlog ? cq : 0;
     const int s = sq;
     const int ls = s >= 0 ? own_slot(a, s) : -1;
@@ -4964,22 +4860,7 @@ __global__ __launch_bounds__(kBS) void k_emit_shard_wide(TickArgs a) {
     }
     if (aall && c > L && rankL < p) aall[S_L + rankL] = s;
     const int64_t exL1 = rbL1 + popc_lt(__ballot(c > L + 1));
-    if (c > 0) {
-        int64_t n_q = c < L ? c : L;
-        if (c > L && rankL < p) n_q += 1;
-        int64_t np = -1;
-        if (c > L) {
-            if (rankL >= p) np = rankL - p;
-            else if (c > L + 1) np = (AL - p) + exL1;
-            if (rankL == p) {
-                a.hout->new_qlen = (AL - p) + exL1;
-                a.hout->n_local = oSL + orankL;
-            }
-        }
-        // the owned worker's next {free, queued} in one 8-byte store (the purge wrote {., 0})
-        if (own) a.free_out[ls] = make_int2(rawq - (int32_t)n_q, np >= 0 ? 1 : 0);
-        if (np >= 0) a.queue_out[np] = s;
-    }
+    if (c > 0) shard_next(a, fill_next(c, L, rankL, p, AL, exL1), s, ls, rawq, oSL + orankL);
 }
 
 // ------------------------------------------------------------ orphan segments

@@ -132,8 +132,8 @@ inline int xc_width(int R) { return R > kRFused ? 2 : 1; }
 
 // The rows of the round table for a largest free count: the smallest power of two >= 32 that
 // holds it, saturating at `limit` (a power of two: kMaxR, sharded kShardMaxR) -- any int32
-// ends the loop, and a count beyond the limit gets the limit's table, which is exact while
-// the fill level leaves two rows (L <= limit - 2)
+// ends the loop, and a count beyond the limit gets the limit's table, which is exact up to
+// the fill level fill_verdict (faasbal_fill.h) accepts
 inline int choose_R(int32_t maxc, int limit = kMaxR) {
     int R = 32;
     while (R < maxc && R < limit) R <<= 1;

@@ -1,9 +1,12 @@
 """Fill levels at every seam of the round table, bit-exact against the oracle.
 
-The water-filling closed form (fill level L, partial round A(L), prefixes S(r)) is written
-seven times; each copy carries the edge rule `maxc > R && L >= R - 1` (a table of R rows is
-exact while L + 2 rows fit).  tests/fill_cases.py builds one tick per seam and
-tests/test_fill_cases.py proves on the CPU that it sits there; here each runs on the GPU and
+The water-filling closed form (fill level L, partial round A(L), prefixes S(r)) is stated once,
+in csrc/faasbal_fill.h -- fill_verdict carries the edge rule `maxc > R && L >= R - 1` (a table
+of R rows is exact while L + 2 rows fit) -- and the seven emissions below call it, each
+finding L in the round table its own way (fill_scan in wave registers; k_emit and
+k_emit_shard_wide their own search).  tests/fill_cases.py builds one tick per seam and
+tests/test_fill_cases.py proves on the CPU that it sits there and that the closed form gives
+the oracle's tick; here each runs on the GPU and
 its outputs, result record (fill_level, max_free, reruns, n_assigned) and committed state
 must equal the oracle's.  fb_timing_read's launch counts say which emission ran ("plan"
 beside "emit": k_plan / k_plan2 ahead of it; "scan2": the sharded recount).
