@@ -1981,6 +1981,69 @@ int fb_log_compact_shard_cancel(fb_ctx *c) {
     return FB_OK;
 }
 
+// Live entries of workers that stay registered completed on the device: count
+// first (k_lr_flag, k_lc_scan write only the scratch), synchronise, check the caller's room,
+// and only then take.  Nothing of the Life changes: the ticks after it make the launches they
+// would have made without it.
+int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out, int32_t *slot_out, int64_t cap,
+                   int64_t *n_reclaimed) {
+    if (!c) return FB_EINVAL;
+    if (below_seq < 0) return fail(c, FB_EINVAL, "below_seq %lld < 0", (long long)below_seq);
+    if ((seq_out || slot_out) && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
+    if (int rc_ = enter(c, life_gate_log_reclaim(c->life, c->caps))) return rc_;
+    HIPCHK(c, hipSetDevice(c->device));
+    const LrPlan p = lr_plan(c->head, below_seq, c->W);
+    if (p.nt == 0 || c->W == 0) {  // (an empty prefix, or no slot to hold a record: nothing is launched)
+        if (n_reclaimed) *n_reclaimed = 0;
+        return FB_OK;
+    }
+    const size_t full = std::max(lc_plan(c->log_cap, c->W_cap, true).bytes, lr_plan(c->log_cap, c->log_cap, c->W_cap).bytes);
+    if (int rc_ = lc_scratch(c, p.bytes, full, 0)) return rc_;
+    char *const base = (char *)c->lc_mem;
+    // (the scratch is idle: every call that uses it waits for its launches before it returns)
+    if (slot_mask && c->W) HIPCHK(c, hipMemcpy(base + p.mask, slot_mask, (size_t)c->W, hipMemcpyHostToDevice));
+    LrArgs a{};
+    a.log = c->log_slot;
+    a.B = p.B;
+    a.W = c->W;
+    a.live_chk = c->life.stale ? 1 : 0;
+    a.reg = c->reg;
+    a.epoch = c->epoch;
+    a.mask = slot_mask ? (const uint8_t *)(base + p.mask) : nullptr;
+    a.t = LcTable{(unsigned long long *)(base + p.tab.bits), (uint32_t *)(base + p.tab.wrel), (uint32_t *)(base + p.tab.tcnt),
+                  (uint32_t *)(base + p.tab.tpre), p.nt};
+    a.seq_out = seq_out ? (int64_t *)(base + p.seq) : nullptr;
+    a.slot_out = slot_out ? (int32_t *)(base + p.slot) : nullptr;
+    a.bud = c->caps.clears == Clears::deferred ? c->bud : nullptr;
+    {
+        Timer t(c, "lr_flag");
+        launch_lr_flag(a, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(a.t, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t n = 0;
+    HIPCHK(c, hipMemcpy(&n, a.t.tpre + p.nt, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)n > p.B)
+        return fail(c, FB_EHIP, "device-reported reclaimed entries %u outside [0, %lld] (the prefix)", n, (long long)p.B);
+    if (n_reclaimed) *n_reclaimed = (int64_t)n;
+    if ((seq_out || slot_out) && cap < (int64_t)n)
+        return fail(c, FB_EINVAL, "the outputs hold %lld entries, the call reclaims %u", (long long)cap, n);
+    if (!n) return FB_OK;
+    {
+        Timer t(c, "lr_take");
+        launch_lr_take(a, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    if (seq_out) HIPCHK(c, hipMemcpy(seq_out, a.seq_out, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (slot_out) HIPCHK(c, hipMemcpy(slot_out, a.slot_out, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return FB_OK;
+}
+
 // The committed pool summarised on the device.  The three launches write only
 // the scratch and the host-mapped record; nothing here settles the log or normalises a window,
 // so the ticks after it make the launches they would have made without it.

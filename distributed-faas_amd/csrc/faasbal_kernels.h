@@ -609,6 +609,22 @@ void launch_lc_scan(const LcTable &t, Stream st);
 void launch_lc_move(const LcArgs &a, bool shard, Stream st);
 void launch_lcs_mark(const LcArgs &a, Stream st);
 void launch_lcs_count(const LcArgs &a, Stream st);
+// fb_log_reclaim (one GPU; grids and the scratch regions: lr_plan, faasbal_layout.h).  Entry
+// q < B is reclaimed iff it is live by LcArgs' rule and (mask) mask[log[q]] != 0.
+struct LrArgs {
+    int32_t *log;                // [head] the entries; the take pass writes -1
+    int64_t B;                   // the prefix walked: min(below_seq, head)
+    int W, live_chk;
+    const uint8_t *reg;
+    const uint32_t *epoch;
+    const uint8_t *mask;         // [W] bytes, or null: every slot
+    LcTable t;                   // over [0, B)
+    int64_t *seq_out;            // [reclaimed] ascending (null: not wanted)
+    int32_t *slot_out;           // [reclaimed] (null: not wanted)
+    int32_t *bud;                // in flight + free per slot (null: the context keeps none)
+};
+void launch_lr_flag(const LrArgs &a, Stream st);
+void launch_lr_take(const LrArgs &a, Stream st);
 // fb_pool_stats (grids, the partial rows' columns and the scratch regions: ps_plan,
 // faasbal_layout.h).  A slot is expired iff it holds a record and (now - hb) > tte (hb_chk:
 // heartbeat contexts; the tick's test); a log entry is live by LcArgs' rule.

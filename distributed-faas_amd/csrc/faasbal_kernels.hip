@@ -5261,6 +5261,100 @@ __global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
     lc_scatter_tile<kShard>(a, tile);
 }
 
+// ------------------------------------------------------------ log reclaim
+// fb_log_reclaim (lr_plan, faasbal_layout.h): the compaction's walk and table over the prefix
+// [0, B) of a one-GPU log.  The walk is given B for its entry count, so that lc_batch's own
+// end test is the prefix test: every load is clamped to B - 1 (B <= head) and a bit at or
+// past B is 0, inside the last word and the last tile too; the epoch test compares the
+// entry's index, which the shorter count does not change.
+// a tile's words of the reclaim bitmap, a wave: lane j < kLcWords gets word j (the other lanes 0)
+template <bool kChk, bool kMask>
+__device__ __forceinline__ unsigned long long lr_flag_tile(const LrArgs &a, int tile) {
+    const int lane = lane_id();
+    const LcWalk w{a.log, nullptr, a.B, a.W, 0, a.reg, a.epoch};
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch], sc[kLcBatch];
+        bool live[kLcBatch];
+        uint8_t mk[kLcBatch];  // the mask byte of the entry's (clamped) slot
+        lc_batch<false, kChk>(w, (int64_t)tile * kLcTile + lane, j0, s, sc, live, [&] {
+#pragma unroll
+            for (int k = 0; k < kLcBatch; ++k) mk[k] = kMask ? a.mask[(uint32_t)sc[k]] : (uint8_t)1;
+        });
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            // (a live entry's slot is its clamped one; a slot past the table names no mask byte)
+            const unsigned long long m = __ballot(live[k] && mk[k] && s[k] == sc[k]);
+            if (lane == j0 + k) mine = m;
+        }
+        if (kChk || kMask) __builtin_amdgcn_sched_barrier(0);
+    }
+    return mine;
+}
+
+// the table but for tpre, over the prefix's tiles; writes only the scratch
+__global__ __launch_bounds__(kBS) void k_lr_flag(LrArgs a) {
+    prefetch_args(a);
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.t.nt) return;  // (the whole wave)
+    unsigned long long mine;
+    if (a.live_chk) mine = a.mask ? lr_flag_tile<true, true>(a, tile) : lr_flag_tile<true, false>(a, tile);
+    else mine = a.mask ? lr_flag_tile<false, true>(a, tile) : lr_flag_tile<false, false>(a, tile);
+    lc_table_tile<true>(a.t, tile, mine);
+}
+
+// The tiles again, as lc_scatter_tile walks them: the entry of a set bit goes to its rank in
+// seq_out / slot_out (ascending: the rank is by index), -1 takes its place in the log, and its
+// slot's budget goes down by one (integer atomics: exact whatever the order).  A word whose set
+// bits all name one slot -- a restarted worker's backlog, a hung worker's burst -- would send up
+// to 64 atomics to one address, which the L2 serialises: such a word sends one, of the word's
+// count (a readfirstlane and a ballot per word decide).  Any other word goes a lane at a time:
+// its addresses differ, so there is nothing to serialise, and a sort to combine the partial
+// runs would cost more than the atomics it saves.
+__global__ __launch_bounds__(kBS) void k_lr_take(LrArgs a) {
+    prefetch_args(a);
+    const int tile = (int)blockIdx.x * kWaves + wave_id();
+    if (tile >= a.t.nt) return;  // (the whole wave)
+    const int lane = lane_id();
+    const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    unsigned long long mine;
+    uint32_t pre;
+    lc_tile_words(a.t, tile, mine, pre);
+    for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
+        int32_t s[kLcBatch];
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            s[k] = a.log[i < a.B ? i : a.B - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < kLcBatch; ++k) {
+            const unsigned long long m = __shfl(mine, j0 + k, 64);
+            const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
+            if (!m) continue;  // (wave-uniform)
+            const bool set = (m >> lane) & 1ull;  // (a set bit: i < B, 0 <= s[k] < W)
+            const int64_t i = i0 + (int64_t)(j0 + k) * 64;
+            if (set) {
+                const int64_t o = (int64_t)p + popc_lt(m);
+                if (a.seq_out) a.seq_out[o] = i;
+                if (a.slot_out) a.slot_out[o] = s[k];
+                a.log[i] = -1;
+            }
+            if (a.bud) {
+                const int first = __builtin_ctzll(m);
+                const int32_t s1 = __shfl(s[k], first, 64);
+                const bool one = __ballot(set && s[k] != s1) == 0ull;
+                if (one) {
+                    if (lane == first) atomicSub(&a.bud[s1], (int32_t)__popcll(m));
+                } else if (set) {
+                    atomicSub(&a.bud[s[k]], 1);
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------ pool summary
 // fb_pool_stats (layout: ps_plan, faasbal_layout.h): reductions and two small histograms over
 // the committed arrays, read only.  Every load is unconditional at a clamped index and masked
@@ -5658,6 +5752,9 @@ void launch_lc_scan(const LcTable &t, Stream st) { lc_launch(k_lc_scan, kLcScanG
 void launch_lc_move(const LcArgs &a, bool shard, Stream st) {
     lc_launch(shard ? k_lc_move<true> : k_lc_move<false>, lc_plan_of(a, shard).move.grid(), a, st);
 }
+// (the grids of lr_plan(head, B, W) depend on B alone)
+void launch_lr_flag(const LrArgs &a, Stream st) { lc_launch(k_lr_flag, lr_plan(a.B, a.B, a.W).flag_grid, a, st); }
+void launch_lr_take(const LrArgs &a, Stream st) { lc_launch(k_lr_take, lr_plan(a.B, a.B, a.W).take_grid, a, st); }
 void launch_lcs_mark(const LcArgs &a, Stream st) { lc_launch(k_lcs_mark, lc_plan_of(a, true).mark_grid, a, st); }
 void launch_lcs_count(const LcArgs &a, Stream st) { lc_launch(k_lcs_count, lc_plan_of(a, true).count_grid, a, st); }
 void launch_ps_slots(const PsArgs &a, Stream st) {

@@ -366,6 +366,42 @@ inline LcPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept) 
 }
 
 // ---------------------------------------------------------------------------------------
+// fb_log_reclaim: the compaction family's walk and table over the prefix [0, B) of a one-GPU
+// log, B = min(below_seq, head), in the compactions' scratch:
+//   k_lr_flag   a workgroup per four tiles of the prefix: the table's bitmap of the entries to
+//               reclaim (whole tiles: bits at or past B are 0), wrel and tcnt
+//   k_lc_scan   as it is: tpre; tpre[nt] is the count the host checks against the caller's cap
+//   k_lr_take   the tile workgroups again: a set bit's sequence and slot go to their rank in
+//               seq / slot, -1 into the log, one off the slot's budget where budgets exist
+// The slot mask (W bytes; read only when the caller gave one) and the two output lists (B
+// entries: the count's bound, known before the count) follow the table.
+struct LrPlan {
+    int64_t B;   // the prefix: min(below_seq, head)
+    int nt;      // its tiles
+    int64_t nw;  // bitmap words
+    int flag_grid, scan_grid, take_grid;
+    LcTableAt tab;
+    size_t mask, seq, slot;  // regions: W, B x 8, B x 4 bytes
+    size_t bytes;
+};
+inline LrPlan lr_plan(int64_t head, int64_t below_seq, int W) {
+    LrPlan p{};
+    p.B = below_seq < head ? below_seq : head;
+    if (p.B < 0) p.B = 0;
+    p.nt = (int)cdiv(p.B, kLcTile);
+    p.nw = (int64_t)p.nt * kLcWords;
+    p.flag_grid = p.take_grid = quarter(p.nt);
+    p.scan_grid = kLcScanGrid;
+    Regions r;
+    p.tab = lc_table_at(r, p.nt, true);
+    p.mask = r.take((size_t)(W > 0 ? W : 0));
+    p.seq = r.take((size_t)p.B * 8);
+    p.slot = r.take((size_t)p.B * 4);
+    p.bytes = r.o;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------
 // fb_pool_stats: three launches, none of which writes anything but the scratch.
 //   k_ps_slots  slot workgroups (kPsTiles tiles of kBS slots each: the counts, sums, minima
 //               and histograms of a row of kPsCols words, and the expired bitmap, a 64-bit

@@ -200,6 +200,30 @@ inline Gate life_gate_pool_stats_shard(const Life &l, const CtxCaps &k) {
     return life_gate(l, one, Call::pool_stats);
 }
 
+// fb_log_reclaim, live entries of workers that stay registered completed between ticks:
+// fb_pool_stats' gate -- the same refusals at every point of a tick, the same flush and undo --
+// with two refusals of its own.  A deque context has no liveness, so nothing to reclaim from.  A
+// sharded context's sequences are global across the ranks: a group form would take the shape
+// of fb_log_compact_shard_mark / _apply (mark, all-reduce, apply), which this is not.  It makes
+// no transition: the Life after a success is the Life before it (a window stays a window, a
+// stale log stale).  (No Call of its own, as fb_pool_stats_shard.)
+inline Gate life_gate_log_reclaim(const Life &l, const CtxCaps &k) {
+    if (k.deque) return Gate{"fb_log_reclaim on a deque context: it keeps no liveness, nothing is in flight on a record", 0u};
+    if (k.sharded)
+        return Gate{"fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (a group form "
+                    "would follow fb_log_compact_shard_mark / _apply)",
+                    0u};
+    Gate g = life_gate(l, k, Call::pool_stats);
+    if (g.refuse) {
+        // (fb_pool_stats' refusals at a point of a tick, under this call's name)
+        if (l.marked) return g;
+        if (l.staged) return Gate{"fb_log_reclaim with staged events pending: launch and commit their tick first", g.duties};
+        if (life_waited(l)) return Gate{"fb_log_reclaim between a tick's wait and its commit: fb_tick_commit first", g.duties};
+        return Gate{"fb_log_reclaim with a tick launched: fb_tick_wait and fb_tick_commit first", g.duties};
+    }
+    return g;
+}
+
 // fb_log_compact_shard_mark, a rank's first half of its group's compaction.  Like a load it
 // discards a tick that was never committed -- waited for (another rank failed), failed or
 // dropped -- after taking its in-place clears back (kUndo; kDiscard: life_lcs_marked).  A tick

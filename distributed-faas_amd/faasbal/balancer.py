@@ -259,6 +259,37 @@ class GpuBalancer:
                                           kept.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return {"n_kept": n.value, "kept": kept[: n.value]}
 
+    def reclaim(self, below_seq=None, slots=None):
+        """fb_log_reclaim: take live log entries back from workers that stay registered (a
+        task that hangs, a worker restarted under its identity): every live entry with a
+        sequence below ``below_seq`` (None: the log head) on one of ``slots`` (an iterable of
+        slots; None: all) is completed on the device and its slot's in-flight count goes down
+        with it; nothing else of the state changes and the tick pipeline stays as it is.
+        Returns dict(n, seq, slot): the reclaimed sequences (int64, ascending) and the slot
+        each was on (int32).  Between ticks, not with staged events."""
+        below = (1 << 62) if below_seq is None else int(below_seq)
+        mask = None
+        if slots is not None:
+            mask = np.zeros(max(self.n_workers, 1), np.uint8)
+            idx = np.asarray(slots if isinstance(slots, np.ndarray) else list(slots), np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= self.n_workers):
+                raise ValueError("slots outside [0, %d)" % self.n_workers)
+            mask[idx] = 1
+        n = C.c_int64()
+        cap = 256
+        while True:
+            seq = np.zeros(max(cap, 1), np.int64)
+            slot = np.zeros(max(cap, 1), np.int32)
+            n.value = -1
+            rc = self.lib.fb_log_reclaim(self.h, below, None if mask is None else mask.ctypes.data_as(C.c_void_p),
+                                         seq.ctypes.data_as(C.c_void_p), slot.ctypes.data_as(C.c_void_p), cap,
+                                         C.byref(n))
+            if rc == _lib.FB_EINVAL and n.value > cap:  # nothing changed: come back with room
+                cap = n.value
+                continue
+            self._chk(rc)
+            return {"n": n.value, "seq": seq[: n.value], "slot": slot[: n.value]}
+
     def pool_stats(self, now, tte, age_edges=()):
         """fb_pool_stats: the committed pool summarised on the device at the clock ``now``
         (expired = registered and ``(now - hb) > tte``, the tick's test): a dict of

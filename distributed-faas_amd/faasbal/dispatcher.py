@@ -81,11 +81,18 @@ class GpuPushDispatcher:
     to be injected (the defaults build exactly what the reference builds:
     ``redis.Redis(host='localhost', port=6379, db=1)`` subscribed to ``tasks``,
     and a bound ZMQ ROUTER with a ``zmq.Poller``).
+
+    ``task_timeout`` (seconds; None: no deadline): a task in flight for longer on a
+    worker that keeps heartbeating is taken back at the top of a tick and dispatched
+    again (fb_log_reclaim).  ``max_attempts`` (None: no bound): a task taken back that
+    many times is recorded FAILED instead.  With both None the loop makes no call,
+    Redis command or message it did not make before.
     """
 
     def __init__(self, ip_address, port, time_to_expire=10, *, max_workers=65536, max_inflight=1 << 24,
                  max_events=65536, device=0, redis_client=None, subscriber=None, socket=None, poller=None,
-                 clock=time.time, tasks_channel="tasks", batch_io=True, balancer=None):
+                 clock=time.time, tasks_channel="tasks", batch_io=True, balancer=None, task_timeout=None,
+                 max_attempts=None):
         self.port = port
         self.batch_io = bool(batch_io)
         self.ip_address = ip_address
@@ -120,6 +127,13 @@ class GpuPushDispatcher:
         # table sharded over several GPUs (same API, see ShardedPushDispatcher)
         self.balancer = balancer if balancer is not None else \
             GpuBalancer(self.max_workers, self.max_inflight, max_events=self.max_events, device=device)
+        self.task_timeout = None if task_timeout is None else float(task_timeout)
+        self.max_attempts = None if max_attempts is None else int(max_attempts)
+        if self.task_timeout is not None and not callable(getattr(self.balancer, "reclaim", None)):
+            raise FaasbalError(FB_ESTATE, "task_timeout needs a balancer with reclaim (fb_log_reclaim): one GPU; "
+                                          "a shard group has none yet")
+        self.reclaimed = 0                             # tasks taken back from live workers
+        self.timed_out_failed = 0                      # ... of which recorded FAILED (max_attempts)
         self._reset_host()
         W = self.max_workers
         self.balancer.load_state(np.zeros(W, np.uint8), np.zeros(W, np.int32), np.zeros(W, np.float64))
@@ -150,6 +164,8 @@ class GpuPushDispatcher:
             raise FaasbalError(-6, "cannot switch the dispatcher loop after %d ticks" % self.ticks)
         if not isinstance(self.balancer, GpuBalancer):
             raise FaasbalError(-6, "the loop without heartbeats runs on a one-GPU balancer")
+        if mode == "deque" and self.task_timeout is not None:
+            raise FaasbalError(-6, "task_timeout needs the heartbeat loop: a deque context keeps no liveness")
         self.balancer.close()
         self.balancer = GpuBalancer(self.max_workers, self.max_inflight, max_events=self.max_events,
                                     device=self.device, mode=mode)
@@ -168,6 +184,8 @@ class GpuPushDispatcher:
         self.head = 0                                  # in-flight log length
         self._last_ts = -np.inf
         self._leaving = collections.deque()            # identities evict() asked to remove, for the next tick
+        self._marks = collections.deque()              # (log head after a tick that dispatched, its clock), ascending
+        self.attempts = {}                             # task_id -> times it was taken back from a live worker
 
     # ------------------------------------------------ reference socket / Redis API
     def bind_socket(self):
@@ -304,7 +322,70 @@ class GpuPushDispatcher:
         self._leaving.extend(worker_ids)
         return [w for w in worker_ids if w in self.slot_of]
 
+    def _take_back(self, seqs):
+        """The host's half of a reclaim: the sequences (ascending) leave the in-flight
+        table, every task counts an attempt; below ``max_attempts`` it goes to the front of
+        the pending tasks in sequence order, the way orphans go back, and at ``max_attempts``
+        it is recorded as the reference's worker records a failed task
+        (``helper_functions.py:24-28``).  Returns (task ids, those recorded FAILED)."""
+        tids, back, failed = [], [], []
+        for q in seqs:
+            ent = self.inflight.pop(int(q), None)
+            if ent is None:
+                raise FaasbalError(FB_ESTATE, "the device reclaimed sequence %d, which the in-flight table lacks" % q)
+            tid = ent[0]
+            self.task_seq.pop(tid, None)
+            n = self.attempts.get(tid, 0) + 1
+            tids.append(tid)
+            if self.max_attempts is not None and n >= self.max_attempts:
+                self.attempts.pop(tid, None)
+                failed.append(tid)
+            else:
+                self.attempts[tid] = n
+                back.append(tid)
+        if back:
+            self.pending.extendleft(reversed(back))
+        if failed:
+            pipe = self._pipe()
+            db = pipe if pipe is not None else self.redis_client
+            for tid in failed:
+                db.hset(tid, mapping={"status": "FAILED", "result": codec.serialize(None)})
+            if pipe is not None:
+                pipe.execute()
+        self.reclaimed += len(tids)
+        self.timed_out_failed += len(failed)
+        return tids, failed
+
+    def reclaim(self, worker_ids):
+        """Take back, now, every task in flight on these identities while their records stay
+        -- a worker that restarted under its identity (``register`` over a live record keeps
+        the registration, ``task_dispatcher.py:347-353``, so no purge would ever return what
+        the previous incarnation held; README.md:264, "if a worker ressucitates"): a hook for
+        a ``register`` from a known identity.  Between ticks.  The tasks go back to the front
+        of the pending ones (or to FAILED at ``max_attempts``); ``evict()`` stays the tool for
+        workers that are gone.  Returns the task ids."""
+        device = getattr(self.balancer, "reclaim", None)
+        if not callable(device):
+            raise FaasbalError(FB_ESTATE, "this balancer has no reclaim (fb_log_reclaim): one GPU only")
+        slots = [self.slot_of[w] for w in worker_ids if w in self.slot_of]
+        if not slots:
+            return []
+        return self._take_back(device(below_seq=None, slots=slots)["seq"])[0]
+
+    def _reclaim_due(self):
+        """Top of a tick with ``task_timeout``: sequences ascend with dispatch time, so the
+        tasks past their deadline are a prefix of the log -- below the head of the newest
+        mark at least ``task_timeout`` old."""
+        due = self._stamp() - self.task_timeout
+        below = None
+        while self._marks and self._marks[0][1] <= due:
+            below = self._marks.popleft()[0]
+        if below is not None and self.inflight and next(iter(self.inflight)) < below:
+            self._take_back(self.balancer.reclaim(below_seq=below)["seq"])
+
     def _run(self, msgs):
+        if self.task_timeout is not None and self._marks:
+            self._reclaim_due()
         # room for every dispatch this tick can make (orphans + pending) before sequence
         # numbers are taken.  Compaction reclaims the finished entries (head - in-flight);
         # when a backlog keeps the worst case above the log even after it, compacting
@@ -395,6 +476,8 @@ class GpuPushDispatcher:
                 if q >= 0 and self.inflight.get(q, (None, -1))[1] == slot[i]:
                     tid, _ = self.inflight.pop(q)
                     self.task_seq.pop(tid, None)
+                    if self.attempts:
+                        self.attempts.pop(tid, None)
         if rpipe is not None:
             rpipe.execute()
         # ---- redistribution: orphans (ascending old sequence) go first
@@ -438,6 +521,8 @@ class GpuPushDispatcher:
         if wpipe is not None:
             wpipe.execute()
         self.head = int(res["log_head"])
+        if self.task_timeout is not None and n:
+            self._marks.append((self.head, now))  # every sequence below it was dispatched by this clock
         # ---- evicted records: their identities become unknown (:246-249)
         for s in out["evicted"]:
             self._release(int(s))
@@ -556,6 +641,7 @@ class GpuPushDispatcher:
                 self.inflight = {remap[q]: v for q, v in self.inflight.items()}
                 self.task_seq = {tid: remap[q] for tid, q in self.task_seq.items()}
                 self.head = int(out["n_kept"])
+                self._remap_marks(out["kept"])
                 self.compactions += 1
                 self.device_compactions += 1
                 return
@@ -568,13 +654,24 @@ class GpuPushDispatcher:
         self.inflight = {remap[q]: v for q, v in self.inflight.items()}
         self.task_seq = {tid: remap[q] for tid, q in self.task_seq.items()}
         self.head = len(keep)
+        self._remap_marks(keep)
         self.compactions += 1
+
+    def _remap_marks(self, kept):
+        """A mark through a compaction's kept list: the survivors below the old value."""
+        if self._marks:
+            new = np.searchsorted(np.asarray(kept, np.int64), [m[0] for m in self._marks], side="left")
+            self._marks = collections.deque((int(h), t) for h, (_, t) in zip(new, self._marks))
 
     def snapshot(self):
         """Host + device state (checkpoint; the reference keeps none)."""
         st = self.balancer.read_state(with_log=True)
         st.update(identity=list(self.identity), inflight=dict(self.inflight), pending=list(self.pending),
                   free_slots=list(self._free_slots), next_slot=self._next_slot)
+        if self._marks:
+            st["marks"] = list(self._marks)
+        if self.attempts:
+            st["attempts"] = dict(self.attempts)
         return st
 
     def restore(self, st):
@@ -601,10 +698,12 @@ class GpuPushDispatcher:
                                                       default=0)))
         used = set(self.slot_of.values())
         self._free_slots = list(st.get("free_slots", [s for s in range(self._next_slot) if s not in used][::-1]))
-        self.inflight = {int(q): (tid, int(s)) for q, (tid, s) in st.get("inflight", {}).items()}
+        self.inflight = {int(q): (tid, int(s)) for q, (tid, s) in sorted(st.get("inflight", {}).items())}
         self.task_seq = {tid: q for q, (tid, _) in self.inflight.items()}
         self.pending = collections.deque(st.get("pending", ()))
         self.head = len(st["log"])
+        self._marks = collections.deque((int(h), float(t)) for h, t in st.get("marks", ()))
+        self.attempts = {tid: int(n) for tid, n in st.get("attempts", {}).items()}
 
 
 def ShardedPushDispatcher(ip_address, port, time_to_expire=10, *, max_workers=65536, max_inflight=1 << 24,

@@ -87,6 +87,9 @@ class ShardedBalancer(GpuBalancer):
     # fb_pool_stats too: a rank cannot answer for the group.  Its part is pool_stats_part;
     # ShardGroup.pool_stats gathers and merges the ranks' parts
     pool_stats = None
+    # fb_log_reclaim as well (global sequences): a group form would follow the compaction's
+    # mark / all-reduce / apply; until then a shard group has no reclaim
+    reclaim = None
 
     def pool_stats_part(self, now, tte, age_edges=()):
         """fb_pool_stats_shard: this rank's part of the group's pool summary as

@@ -207,6 +207,36 @@ int fb_log_compact_shard_apply(fb_ctx *ctx, int64_t n_live_global, int64_t *kept
                                int64_t *n_kept_local);
 int fb_log_compact_shard_cancel(fb_ctx *ctx);
 
+/* One-GPU heartbeat contexts (both kinds of clears: with in-flight counts and, past 128 K slots,
+ * without), between ticks: take live log entries back from workers that stay registered -- a
+ * worker restarted under its identity, a task that hangs while its worker heartbeats on; no
+ * purge ever fires for either.  Let B = min(below_seq, log_head).  Entry q is reclaimed iff
+ * q < B, it is live by fb_log_compact's rule (log_slot[q] >= 0, its slot holds a record and
+ * q >= epoch[slot]: entries that lazy commits left behind are not live), and slot_mask == NULL
+ * or slot_mask[log_slot[q]] != 0 (slot_mask: n_workers host bytes).  Sequences ascend with
+ * dispatch time, so "dispatched before a clock" is a prefix and "of these workers" a mask.
+ * Effect: log_slot[q] = -1 for every reclaimed q; where in-flight counts exist
+ * (fb_read_inflight) each slot's count drops by the number of its reclaimed entries while its
+ * free count stays, so the slot's budget (free + in flight) goes down with the log.  Nothing
+ * else of the committed state changes (records, heartbeats, epochs, free counts, the queue /
+ * window, log_head, round hints), and the tick pipeline keeps its state (a window stays a
+ * window): the state afterwards is the one fb_load_state installs from fb_read_state's arrays
+ * with those entries set to -1.  Hence a later result whose seq names a reclaimed entry is an
+ * ordinary result that completes nothing, and a later death of the worker does not list the
+ * reclaimed entries among its orphans.
+ * seq_out / slot_out (either or both may be NULL; cap entries each): the reclaimed sequences,
+ * ascending, and the slot each was on.  *n_reclaimed (may be NULL) is set as soon as the count
+ * is known, which is before anything but scratch is written: with an output given and
+ * cap < the count, FB_EINVAL, nothing changes and *n_reclaimed holds the count to come back
+ * with.  below_seq < 0: FB_EINVAL.
+ * FB_ESTATE: a deque context (no liveness), a sharded context (its sequences are global across
+ * ranks; a group form would follow fb_log_compact_shard_mark / _apply), and out of order, as
+ * fb_pool_stats.
+ * Answers what the reference leaves open, which keeps no log: "if something happens with the
+ * worker, the task is gone", "if a worker ressucitates" (README.md:263-264). */
+int fb_log_reclaim(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out,
+                   int32_t *slot_out, int64_t cap, int64_t *n_reclaimed);
+
 /* One-GPU contexts (heartbeat and deque), between ticks: a summary of the committed worker pool
  * at the clock `now`, computed where the state lives (three launches, a few hundred bytes back;
  * DESIGN.md §5e).  A slot is expired iff it is registered and (now - last_heartbeat) > tte, the

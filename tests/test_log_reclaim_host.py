@@ -1,0 +1,178 @@
+"""fb_log_reclaim without a GPU.
+
+1. The numpy model of its rule (tests/reclaim_model.py) against an entry-by-entry brute force.
+2. lr_plan (csrc/faasbal_layout.h), walked on the CPU by tests/lr_probe.cpp and compared with
+   the plan recomputed here: the grids cover the prefix [0, min(below_seq, head)) exactly, the
+   scratch regions hold what the passes touch and do not overlap.
+3. life_gate_log_reclaim (csrc/faasbal_life.h), walked by tests/life_reclaim_probe.cpp over
+   every point of a tick's life and every context kind; csrc/faasbal_api.hip calls that gate;
+   the library declares, exports and binds the symbol.
+"""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from reclaim_model import inflight_model, live_entries, reclaim_model, slots_mask
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+CSRC = os.path.join(REPO, "distributed-faas_amd", "csrc")
+
+
+# --------------------------------------------------------------------------- the model
+def _random_state(rng, W, head):
+    reg = (rng.random(W) < 0.7).astype(np.uint8)
+    epoch = np.where(rng.random(W) < 0.5, 0, rng.integers(0, head + 2, W)).astype(np.uint32)
+    log = rng.integers(0, W, head).astype(np.int32)
+    log[rng.random(head) < 0.3] = -1
+    return dict(reg=reg, free=rng.integers(0, 4, W).astype(np.int32), hb=np.zeros(W), epoch=epoch,
+                queue=np.zeros(0, np.int32), log=log, head=head)
+
+
+def _brute(st, below, mask):
+    log = [int(x) for x in st["log"]]
+    seq, slot = [], []
+    for q, s in enumerate(log):
+        if below is not None and q >= below:
+            continue
+        if s < 0 or not st["reg"][s] or q < int(st["epoch"][s]):
+            continue
+        if mask is not None and not mask[s]:
+            continue
+        seq.append(q)
+        slot.append(s)
+        log[q] = -1
+    return log, seq, slot
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_model_against_brute_force(seed):
+    rng = np.random.default_rng(seed)
+    W, head = int(rng.integers(1, 40)), int(rng.integers(0, 300))
+    st = _random_state(rng, W, head)
+    before = inflight_model(st)
+    for below in (None, 0, 1, head // 2, head, head + 7):
+        for mask in (None, np.zeros(W, np.uint8), slots_mask(W, [W // 2]), (rng.random(W) < 0.5).astype(np.uint8)):
+            new, seq, slot, drop = reclaim_model(st, below, mask)
+            log, bseq, bslot = _brute(st, below, mask)
+            assert new["log"].tolist() == log and seq.tolist() == bseq and slot.tolist() == bslot
+            assert seq.dtype == np.int64 and slot.dtype == np.int32
+            # the per-slot counts: what was live on the slot, less what was taken from it
+            assert np.array_equal(inflight_model(new), before - drop)
+            assert drop.tolist() == [bslot.count(s) for s in range(W)]
+            # nothing else of the state changes, and the input is left alone
+            assert all(new[k] is st[k] for k in st if k != "log")
+            assert not live_entries(new)[seq].any()
+    with pytest.raises(ValueError):
+        reclaim_model(st, -1)
+
+
+# --------------------------------------------------------------------------- the plan
+def _build(tmp, src, name, extra=()):
+    if shutil.which("hipcc") is None:
+        pytest.fail("hipcc not found: %s cannot be compiled" % src)
+    exe = str(tmp / name)
+    subprocess.run(["hipcc", "-std=c++17", "-O1", *extra, "-I" + CSRC, "-I" + os.path.join(REPO, "include"),
+                    os.path.join(HERE, src), "-o", exe], check=True)
+    return exe
+
+
+SEAMS = (0, 1, 63, 64, 65, 2047, 2048, 2049, 3 * 2048 + 5)
+
+
+def _r256(b):
+    return (b + 255) & ~255
+
+
+def test_plan_is_the_one_recomputed_here(tmp_path):
+    exe = _build(tmp_path, "lr_probe.cpp", "lr_probe")
+    cases = [(h, b, W) for h in SEAMS for b in SEAMS + (h + 7,) for W in (0, 1, 300)]
+    cases.append((1 << 24, 1 << 23, 1 << 17))
+    text = "".join("%d %d %d\n" % c for c in cases)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout
+    rows = [{k: int(v) for k, v in (kv.split("=") for kv in line.split())} for line in out.splitlines()]
+    assert len(rows) == len(cases)
+    assert any(b > h for h, b, _ in cases)  # below > head is walked
+    for (head, below, W), r in zip(cases, rows):
+        what = "head %d below %d W %d" % (head, below, W)
+        B = min(head, below)
+        nt = -(-B // 2048)
+        assert (r["tile"], r["words_per_tile"]) == (2048, 32), what
+        assert (r["B"], r["nt"], r["nw"]) == (B, nt, 32 * nt), what
+        assert r["flag_grid"] == r["take_grid"] == -(-nt // 4) and r["scan_grid"] == 1, what
+        assert r["flag.cover"] == r["take.cover"] == r["words.cover"] == 1, what
+        # the scratch recomputed: the table, the mask, the two lists, front to back at 256-byte offsets
+        at, o = {}, 0
+        for key, nbytes in (("bitmap", 8 * 32 * nt), ("wrel", 4 * 32 * nt), ("tcnt", 4 * nt), ("tpre", 4 * (nt + 1)),
+                            ("mask", W), ("seq", 8 * B), ("slot", 4 * B)):
+            at[key] = o
+            o += _r256(nbytes)
+        assert {k: r[k] for k in at} == at and r["bytes"] == o, what
+
+
+# --------------------------------------------------------------------------- the gate
+IN_TICK = ("phase1", "launched", "waited", "failed")
+
+
+def _check_gate(exe, env=None):
+    out = subprocess.run([exe], capture_output=True, text=True, check=True, env=env).stdout
+    rows = []
+    for line in out.splitlines():
+        head, _, refuse = line.partition(" refuse=")
+        r = dict(kv.split("=") for kv in head.split())
+        r["refuse"] = None if refuse == "-" else refuse
+        rows.append(r)
+    assert len(rows) == 4 * 2 * 6 * 2 * 2
+    assert len({(r["kind"], r["staged"], r["pos"], r["cm"], r["undo_E"]) for r in rows}) == len(rows)
+    for r in rows:
+        what = str(r)
+        assert r["same_life"] == "1", what  # no transition
+        duties = set() if r["duties"] == "-" else set(r["duties"].split(","))
+        if r["kind"] == "deque":
+            assert r["refuse"] and "deque" in r["refuse"] and duties <= {"flush"}, what
+        elif r["kind"] == "shard":
+            assert r["refuse"] and "sharded" in r["refuse"] and "fb_log_compact_shard_mark" in r["refuse"], what
+            assert duties <= {"flush"}, what
+        elif r["staged"] == "1" or r["pos"] in IN_TICK:
+            # the refusals of fb_pool_stats at every point of a tick
+            assert r["refuse"] and r["refuse"].startswith("fb_log_reclaim") and duties <= {"flush"}, what
+            assert r["ps_refused"] == "1", what
+        else:  # between ticks (none; dropped: a launch the wait dropped, its in-place clears owed)
+            assert r["refuse"] is None and r["ps_refused"] == "0", what
+            want = set()
+            if r["cm"] == "1":
+                want.add("flush")
+            if r["pos"] == "dropped" and r["undo_E"] != "0":
+                want.add("undo")
+            assert duties == want, what
+            assert r["duties"] == r["ps_duties"], what  # fb_pool_stats' duties
+
+
+def test_gate_refusals_and_duties(tmp_path):
+    _check_gate(_build(tmp_path, "life_reclaim_probe.cpp", "life_reclaim_probe"))
+
+
+def test_gate_probe_under_sanitizers(tmp_path):
+    exe = _build(tmp_path, "life_reclaim_probe.cpp", "life_reclaim_probe_san",
+                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
+    _check_gate(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
+
+
+def test_api_calls_the_gate_and_the_binding_knows_the_symbol():
+    api = open(os.path.join(CSRC, "faasbal_api.hip")).read()
+    body = api[api.index("int fb_log_reclaim(fb_ctx *c"):]
+    body = body[:body.index("\n}\n")]
+    assert re.search(r"enter\(c,\s*life_gate_log_reclaim\(c->life,\s*c->caps\)\)", body)
+    # ... ahead of every launch and every write
+    assert body.index("life_gate_log_reclaim") < body.index("launch_lr_flag") < body.index("launch_lc_scan") \
+        < body.index("cap < (int64_t)n") < body.index("launch_lr_take")
+    header = open(os.path.join(REPO, "include", "faasbal.h")).read()
+    assert "int fb_log_reclaim(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mask" in header
+    from faasbal import _lib
+    assert "fb_log_reclaim" in _lib.EXPORTS
+    from faasbal.balancer import GpuBalancer
+    assert callable(GpuBalancer.reclaim)
