@@ -22,6 +22,7 @@
 #include "faasbal.h"
 #include "faasbal_kernels.h"
 #include "faasbal_life.h"
+#include "faasbal_load.h"
 #include "faasbal_plan.h"
 
 using namespace fb;
@@ -1442,6 +1443,67 @@ int create_ctx(fb_ctx **out, int32_t max_workers, int64_t max_log, int32_t max_e
     *out = c;
     return FB_OK;
 }
+
+static_assert(sizeof(LoadPair) == sizeof(int2), "free_[] holds {free_processes, queued} pairs");
+
+// fb_load_state / fb_load_shard behind their gates: faasbal_load.h's check (all of it before the
+// first wait or copy: a rejected load changes nothing), its image onto the device, and every
+// host field that describes the committed state.
+int load_install(fb_ctx *c, const LoadIn &in) {
+    const LoadKind k{c->deque != 0, c->shard != 0, c->caps.clears == Clears::deferred, c->win_cap,
+                     c->W_cap, c->W_global, c->Wq_cap, c->log_cap};
+    std::string msg;
+    if (int rc = load_check(k, in, msg)) return fail(c, rc, "%s", msg.c_str());
+    const LoadImage m = load_image(k, in);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, stream_wait(c));
+#define FB_UP(dst, src, n)                                                                        \
+    if (n) HIPCHK(c, hipMemcpy((dst), (src), (size_t)(n) * sizeof *(dst), hipMemcpyHostToDevice))
+    const size_t W = (size_t)in.n_workers;
+    FB_UP(c->pos_of[0], m.pos.data(), m.pos.size());
+    FB_UP(c->reg, m.reg.data(), W);
+    FB_UP(c->free_[0], (const int2 *)m.fq.data(), W);
+    FB_UP(c->hb, m.hb.data(), W);
+    FB_UP(c->epoch, m.epoch.data(), W);
+    FB_UP(c->queue[0], in.queue, in.queue_len);
+    FB_UP(c->qfree[0], m.qfree.data(), m.qfree.size());
+    FB_UP(c->qhb[0], m.qhb.data(), m.qhb.size());
+    FB_UP(c->tokcnt[0], m.tokcnt.data(), m.tokcnt.size());
+    if (c->deque && W) {  // no token served yet: qrank is each token's place among its slot's
+        HIPCHK(c, hipMemset(c->xw[0], 0, W * 4));
+        HIPCHK(c, hipMemset(c->kl[0], 0, W * 4));
+    }
+    FB_UP(c->qrank[0], m.qrank.data(), m.qrank.size());
+    FB_UP(c->log_slot, m.log.data(), m.log.size());
+    FB_UP(c->lseq, in.log_seq, c->shard ? in.log_len : 0);
+    FB_UP(c->bud, m.bud.data(), m.bud.size());
+#undef FB_UP
+    // the committed buffers are the ones just written, the queue a dense one from position 0
+    c->cur = 0;
+    c->qcur = 0;
+    c->qoff = 0;
+    c->slot_base = in.slot_base;
+    c->W = in.n_workers;
+    c->Qn = in.queue_len;
+    c->head = in.log_head;
+    c->head_local = c->shard ? in.log_len : 0;  // (one GPU: the log is [0, head), this stays 0)
+    c->tick += 1;
+    // what only some kinds read; a load writes each all the same, with the value that kind keeps:
+    c->pos_ok = c->win_cap;      // window contexts: pos_of[0] above is exact (others: always false)
+    c->qaos = c->caps.lists;     // one-GPU heartbeat: qfree / qhb above describe the queue (others: always false)
+    c->Qtrue = in.queue_len;     // read by window and one-GPU code only (a shard's commits write it, nothing reads it)
+    c->last_L = -1;              // plan_window's inputs: it answers "no" for a shard or a deque
+    c->last_O = 0;               // before it reads them
+    c->shard_R = 0;              // sharded: a wide table kept for the replaced state's fill level, or
+                                 // asked by its relaunch (one GPU: always 0, read behind c->shard only)
+    // the first tick's round table.  Sharded: from what every rank knows alike (the exchange
+    // layout depends on it): its events' values and fb_set_round_hint (the loaded state's global
+    // max free count, which the caller knows from the global state); the rank's own max (m.maxc)
+    // would differ between ranks.  A fill level beyond it relaunches wider.
+    c->maxc_hint = c->shard ? 1 : m.maxc;
+    life_replaced(c->life);
+    return FB_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1513,105 +1575,9 @@ int fb_load_state(fb_ctx *c, int32_t n_workers, const uint8_t *registered, const
                   const int32_t *log_slot, int64_t log_len) {
     if (!c) return FB_EINVAL;
     if (int rc_ = enter(c, Call::load_state)) return rc_;
-    if (n_workers < 0 || n_workers > c->W_cap) return fail(c, FB_EINVAL, "n_workers %d outside [0, %d]", n_workers, c->W_cap);
-    if (log_len < 0 || log_len > c->log_cap) return fail(c, FB_EINVAL, "log_len %lld exceeds capacity", (long long)log_len);
-    if (queue_len < 0 || queue_len > (c->deque ? c->Wq_cap : n_workers))
-        return fail(c, FB_EINVAL, "queue_len %lld", (long long)queue_len);
-    const size_t W = (size_t)n_workers;
-    std::vector<uint8_t> inq(W ? W : 1, 0);
-    std::vector<int32_t> tokcnt(c->deque ? (W ? W : 1) : 0, 0);
-    std::vector<uint32_t> qrank(c->deque ? (size_t)queue_len : 0);
-    int32_t maxc = 1;
-    for (int64_t i = 0; i < queue_len; ++i) {
-        const int32_t s = queue[i];
-        if (s < 0 || s >= n_workers || !registered[s] || (inq[s] && !c->deque))
-            return fail(c, FB_EINVAL, "queue[%lld] = %d is out of range, unregistered or duplicated", (long long)i, s);
-        inq[s] = 1;
-        maxc = std::max(maxc, free_processes[s]);
-        if (c->deque) qrank[i] = (uint32_t)(++tokcnt[s]) | kPart2;  // rank among the slot's tokens
-    }
-    for (int64_t i = 0; i < log_len; ++i)
-        if (log_slot[i] < -1 || log_slot[i] >= n_workers)
-            return fail(c, FB_EINVAL, "log_slot[%lld] = %d out of range", (long long)i, log_slot[i]);
-    std::vector<uint8_t> reg(W ? W : 1, 0);
-    std::vector<double> hbv(W ? W : 1);
-    std::vector<uint32_t> epv(W ? W : 1);
-    for (size_t s = 0; s < W; ++s) {
-        reg[s] = registered[s] ? 1 : 0;
-        hbv[s] = reg[s] ? last_heartbeat[s] : __builtin_nan("");  // no record: NaN (never "dead")
-        epv[s] = epoch ? epoch[s] : 0u;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, stream_wait(c));
-    c->cur = 0;
-    c->qcur = 0;
-    c->qoff = 0;
-    if (c->win_cap && W) {
-        // a queued slot's position (others: never read)
-        std::vector<int32_t> pos(W, 0);
-        for (int64_t i = 0; i < queue_len; ++i) pos[queue[i]] = (int32_t)i;
-        HIPCHK(c, hipMemcpy(c->pos_of[0], pos.data(), W * 4, hipMemcpyHostToDevice));
-    }
-    c->pos_ok = c->win_cap;
-    if (W) {
-        HIPCHK(c, hipMemcpy(c->reg, reg.data(), W, hipMemcpyHostToDevice));
-        std::vector<int2> fq(W);
-        for (size_t s = 0; s < W; ++s) fq[s] = make_int2(free_processes[s], inq[s]);
-        HIPCHK(c, hipMemcpy(c->free_[0], fq.data(), W * sizeof(int2), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->hb, hbv.data(), W * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->epoch, epv.data(), W * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (queue_len) {
-        HIPCHK(c, hipMemcpy(c->queue[0], queue, (size_t)queue_len * 4, hipMemcpyHostToDevice));
-        std::vector<int32_t> qf((size_t)queue_len);
-        std::vector<double> qh((size_t)queue_len);
-        for (int64_t i = 0; i < queue_len; ++i) {
-            qf[i] = free_processes[queue[i]];
-            qh[i] = last_heartbeat[queue[i]];
-        }
-        HIPCHK(c, hipMemcpy(c->qfree[0], qf.data(), (size_t)queue_len * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->qhb[0], qh.data(), (size_t)queue_len * 8, hipMemcpyHostToDevice));
-    }
-    c->qaos = !c->deque;
-    if (c->deque) {
-        if (W) {
-            HIPCHK(c, hipMemcpy(c->tokcnt[0], tokcnt.data(), W * 4, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemset(c->xw[0], 0, W * 4));
-            HIPCHK(c, hipMemset(c->kl[0], 0, W * 4));
-        }
-        if (queue_len) HIPCHK(c, hipMemcpy(c->qrank[0], qrank.data(), (size_t)queue_len * 4, hipMemcpyHostToDevice));
-    }
-    if (log_len) {
-        // heartbeat contexts keep only live entries of current registrations in the log:
-        // an entry of a slot without a record, or older than its registration's epoch,
-        // can never be redistributed (build-defined)
-        std::vector<int32_t> lg(log_slot, log_slot + log_len);
-        if (!c->deque)
-            for (int64_t i = 0; i < log_len; ++i)
-                if (lg[i] >= 0 && (!reg[lg[i]] || (uint64_t)i < (uint64_t)epv[lg[i]])) lg[i] = -1;
-        HIPCHK(c, hipMemcpy(c->log_slot, lg.data(), (size_t)log_len * 4, hipMemcpyHostToDevice));
-        if (c->caps.clears == Clears::deferred) {
-            std::vector<int32_t> bud(W ? W : 1, 0);
-            for (int64_t i = 0; i < log_len; ++i)
-                if (lg[i] >= 0) ++bud[lg[i]];
-            for (size_t s = 0; s < W; ++s) bud[s] = reg[s] ? (int32_t)((uint32_t)bud[s] + (uint32_t)free_processes[s]) : 0;
-            if (W) HIPCHK(c, hipMemcpy(c->bud, bud.data(), W * 4, hipMemcpyHostToDevice));
-        }
-    } else if (c->caps.clears == Clears::deferred && W) {
-        std::vector<int32_t> bud(W);
-        for (size_t s = 0; s < W; ++s) bud[s] = reg[s] ? free_processes[s] : 0;
-        HIPCHK(c, hipMemcpy(c->bud, bud.data(), W * 4, hipMemcpyHostToDevice));
-    }
-    c->W = n_workers;
-    c->Qn = queue_len;
-    c->Qtrue = queue_len;
-    c->head = log_len;
-    c->tick += 1;
-    c->maxc_hint = maxc;
-    c->last_L = -1;
-    c->last_O = 0;
-    life_replaced(c->life);
-    return FB_OK;
+    // the shard case with slot_base = 0, the entry's index for its sequence and log_head = log_len
+    return load_install(c, LoadIn{0, n_workers, registered, free_processes, last_heartbeat, epoch, queue, queue_len,
+                                  log_slot, nullptr, log_len, log_len});
 }
 
 int fb_read_state(fb_ctx *c, uint8_t *registered, int32_t *free_processes, double *last_heartbeat, uint32_t *epoch,
@@ -1657,88 +1623,8 @@ int fb_load_shard(fb_ctx *c, int32_t slot_base, int32_t n_workers, const uint8_t
                   int64_t log_len, int64_t log_head) {
     if (!c) return FB_EINVAL;
     if (int rc_ = enter(c, Call::load_shard)) return rc_;
-    if (n_workers < 0 || n_workers > c->W_cap || slot_base < 0 || (int64_t)slot_base + n_workers > c->W_global)
-        return fail(c, FB_EINVAL, "slot range [%d, %d + %d) outside the %d-slot table", slot_base, slot_base, n_workers,
-                    c->W_global);
-    if (log_len < 0 || log_len > c->log_cap || log_head < log_len || log_head >= ((int64_t)1 << 31))
-        return fail(c, FB_EINVAL, "log_len %lld / log_head %lld", (long long)log_len, (long long)log_head);
-    if (queue_len < 0 || queue_len > c->W_global) return fail(c, FB_EINVAL, "queue_len %lld", (long long)queue_len);
-    const size_t W = (size_t)n_workers;
-    std::vector<uint8_t> inq(W ? W : 1, 0), seen((size_t)c->W_global, 0);
-    int32_t maxc = 1;
-    for (int64_t i = 0; i < queue_len; ++i) {
-        const int32_t s = queue[i];
-        if (s < 0 || s >= c->W_global || seen[s])
-            return fail(c, FB_EINVAL, "queue[%lld] = %d is out of range or duplicated", (long long)i, s);
-        seen[s] = 1;
-        const int32_t ls = s - slot_base;
-        if (ls >= 0 && ls < n_workers) {
-            if (!registered[ls]) return fail(c, FB_EINVAL, "queue[%lld] = %d is not registered", (long long)i, s);
-            inq[ls] = 1;
-            maxc = std::max(maxc, free_processes[ls]);
-        }
-    }
-    for (int64_t i = 0; i < log_len; ++i) {
-        const int32_t s = log_slot[i];
-        if (s < -1 || (s >= 0 && (s < slot_base || s >= slot_base + n_workers)))
-            return fail(c, FB_EINVAL, "log_slot[%lld] = %d is not one of this rank's slots", (long long)i, s);
-        if ((int64_t)log_seq[i] >= log_head || (i && log_seq[i] <= log_seq[i - 1]))
-            return fail(c, FB_EINVAL, "log_seq must ascend below log_head (entry %lld)", (long long)i);
-    }
-    std::vector<uint8_t> reg(W ? W : 1, 0);
-    std::vector<double> hbv(W ? W : 1);
-    std::vector<uint32_t> epv(W ? W : 1);
-    for (size_t s = 0; s < W; ++s) {
-        reg[s] = registered[s] ? 1 : 0;
-        hbv[s] = reg[s] ? last_heartbeat[s] : __builtin_nan("");  // no record: NaN (never "dead")
-        epv[s] = epoch ? epoch[s] : 0u;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, stream_wait(c));
-    c->cur = 0;
-    c->qcur = 0;
-    c->qoff = 0;
-    c->qcur = 0;
-    c->qoff = 0;
-    if (c->win_cap && W) {
-        // a queued slot's position (others: never read)
-        std::vector<int32_t> pos(W, 0);
-        for (int64_t i = 0; i < queue_len; ++i) pos[queue[i]] = (int32_t)i;
-        HIPCHK(c, hipMemcpy(c->pos_of[0], pos.data(), W * 4, hipMemcpyHostToDevice));
-    }
-    if (W) {
-        HIPCHK(c, hipMemcpy(c->reg, reg.data(), W, hipMemcpyHostToDevice));
-        std::vector<int2> fq(W);
-        for (size_t s = 0; s < W; ++s) fq[s] = make_int2(free_processes[s], inq[s]);
-        HIPCHK(c, hipMemcpy(c->free_[0], fq.data(), W * sizeof(int2), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->hb, hbv.data(), W * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->epoch, epv.data(), W * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (queue_len) HIPCHK(c, hipMemcpy(c->queue[0], queue, (size_t)queue_len * 4, hipMemcpyHostToDevice));
-    if (log_len) {
-        // live entries of current registrations only (see fb_load_state)
-        std::vector<int32_t> lg(log_slot, log_slot + log_len);
-        for (int64_t i = 0; i < log_len; ++i)
-            if (lg[i] >= 0 && (!reg[lg[i] - slot_base] || (uint64_t)log_seq[i] < (uint64_t)epv[lg[i] - slot_base]))
-                lg[i] = -1;
-        HIPCHK(c, hipMemcpy(c->log_slot, lg.data(), (size_t)log_len * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->lseq, log_seq, (size_t)log_len * 4, hipMemcpyHostToDevice));
-    }
-    c->slot_base = slot_base;
-    c->W = n_workers;
-    c->Qn = queue_len;
-    c->head = log_head;
-    c->head_local = log_len;
-    c->tick += 1;
-    // the first tick's round table from what every rank knows alike (the exchange layout
-    // depends on it): its events' values and fb_set_round_hint (the loaded state's global
-    // max free count, which the caller knows from the global state); the rank's own max
-    // (maxc above) would differ between ranks.  A fill level beyond it relaunches wider.
-    (void)maxc;
-    c->maxc_hint = 1;
-    c->shard_R = 0;  // (a wide table kept for the replaced state's fill level, or asked by its relaunch)
-    life_replaced(c->life);
-    return FB_OK;
+    return load_install(c, LoadIn{slot_base, n_workers, registered, free_processes, last_heartbeat, epoch, queue,
+                                  queue_len, log_slot, log_seq, log_len, log_head});
 }
 
 int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {

@@ -19,7 +19,7 @@ def build_lib(verbose=False, out=None, defines=()):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "faasbal_kernels.h"), os.path.join(CSRC, "faasbal_plan.h"),
             os.path.join(CSRC, "faasbal_layout.h"), os.path.join(CSRC, "faasbal_life.h"),
-            os.path.join(CSRC, "faasbal_fill.h"),
+            os.path.join(CSRC, "faasbal_fill.h"), os.path.join(CSRC, "faasbal_load.h"),
             os.path.join(REPO, "include", "faasbal.h")]
     stamp = OUT_ + ".defines"
     want = " ".join(sorted(defines))

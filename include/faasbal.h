@@ -127,7 +127,15 @@ const char *fb_last_error(const fb_ctx *ctx);
 /* Install a worker-table state (replaces building self.workers and the
  * free_workers OrderedDict by hand, task_dispatcher.py:194, :327).
  * queue: slots in LRU order (front first), each registered, no duplicates.
- * log_slot: worker slot per in-flight task sequence number (-1 = completed). */
+ * log_slot: worker slot per in-flight task sequence number (-1 = completed).
+ * What a state must satisfy and what the device receives of it is stated once, for this
+ * call and fb_load_shard, in csrc/faasbal_load.h (load_check, load_image): on
+ * heartbeat contexts an entry is kept only if its slot holds a record and its sequence is
+ * at or above the slot's epoch (load_entry_live), a deque keeps every entry.  A state that
+ * fails a condition is refused with FB_EINVAL, the first failing condition in
+ * fb_last_error, and nothing changes.  epoch may be NULL (every epoch 0); any other array
+ * that is NULL while its count (n_workers, queue_len, log_len) is above zero is refused in
+ * the same way; with a count of zero the array is not read and may be NULL. */
 int fb_load_state(fb_ctx *ctx, int32_t n_workers, const uint8_t *registered,
                   const int32_t *free_processes, const double *last_heartbeat,
                   const uint32_t *epoch, const int32_t *queue, int64_t queue_len,
@@ -148,7 +156,8 @@ int fb_read_inflight(fb_ctx *ctx, uint32_t *inflight);
 
 /* One-GPU contexts (heartbeat and deque), between ticks: renumber the in-flight log densely.
  * Entry q survives iff it is live: log_slot[q] >= 0 and, on heartbeat contexts, its slot holds a
- * record and q >= epoch[slot] (the rule of k_log_normalize / fb_load_state).  Survivors keep their
+ * record and q >= epoch[slot] (the rule a load applies: load_entry_live, csrc/faasbal_load.h;
+ * k_log_normalize's on the device).  Survivors keep their
  * order; new sequence = number of survivors below q.  Every slot's epoch becomes the number of
  * survivors below min(epoch, log_head).  log_head becomes *n_kept.  Nothing else of the committed
  * state changes (records, queue / window, free counts, in-flight counts, round hints), and the
@@ -179,7 +188,7 @@ int fb_log_compact(fb_ctx *ctx, int64_t expect_kept, int64_t *kept_seq, int64_t 
  * size.  Every one of the size's bytes is written (bits at or past log_head: 0).  Bit q is set
  * iff q is the sequence of one of this rank's entries and the entry is live by fb_log_compact's
  * rule (log_slot[i] >= 0 and, where entries of dead registrations may be in the log, the slot
- * holds a record and log_seq[i] >= epoch[slot]).  *n_live_local: this rank's live entries.  The
+ * holds a record and log_seq[i] >= epoch[slot]: load_entry_live).  *n_live_local: this rank's live entries.  The
  * committed state and the tick pipeline stay as they are.  An uncommitted tick is discarded, as
  * fb_load_shard discards it (a tick waited for and not committed because another rank failed, a
  * tick whose wait failed): its in-place clears are taken back first, so the entries its results
@@ -212,7 +221,7 @@ int fb_log_compact_shard_cancel(fb_ctx *ctx);
  * worker restarted under its identity, a task that hangs while its worker heartbeats on; no
  * purge ever fires for either.  Let B = min(below_seq, log_head).  Entry q is reclaimed iff
  * q < B, it is live by fb_log_compact's rule (log_slot[q] >= 0, its slot holds a record and
- * q >= epoch[slot]: entries that lazy commits left behind are not live), and slot_mask == NULL
+ * q >= epoch[slot], load_entry_live: entries that lazy commits left behind are not live), and slot_mask == NULL
  * or slot_mask[log_slot[q]] != 0 (slot_mask: n_workers host bytes).  Sequences ascend with
  * dispatch time, so "dispatched before a clock" is a prefix and "of these workers" a mask.
  * Effect: log_slot[q] = -1 for every reclaimed q; where in-flight counts exist
@@ -553,7 +562,9 @@ int fb_create_deque(fb_ctx **out, int32_t max_workers, int64_t max_tokens, int64
 int fb_create_sharded(fb_ctx **out, int32_t max_workers_local, int32_t n_workers_global,
                       int64_t max_log_local, int32_t max_events, int device, int32_t rank, int32_t world);
 /* queue: global slots in LRU order; log_slot: global slot per local entry
- * (-1 completed); log_seq: its global sequence number; log_head: global log length. */
+ * (-1 completed); log_seq: its global sequence number; log_head: global log length.
+ * Checked and installed by the statement fb_load_state names (csrc/faasbal_load.h), null
+ * arrays included (log_seq with log_len > 0, too); the kinds' differences are listed there. */
 int fb_load_shard(fb_ctx *ctx, int32_t slot_base, int32_t n_workers, const uint8_t *registered,
                   const int32_t *free_processes, const double *last_heartbeat, const uint32_t *epoch,
                   const int32_t *queue, int64_t queue_len, const int32_t *log_slot, const uint32_t *log_seq,
