@@ -1746,9 +1746,11 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
 }
 
 // A shard group's compaction, this rank's two halves.
-// (the scratch of a full log: lc_scratch's bound)
+// (the scratch of a full log: lc_scratch's bound, for the compaction's halves and for
+// fb_log_reclaim_shard, which shares the allocation)
 static size_t lcs_full_bytes(const fb_ctx *c) {
-    return lcs_plan(std::max<int64_t>(c->head, (int64_t)c->log_cap * c->world), c->log_cap, c->W_cap, true).bytes;
+    return std::max(lcs_plan(std::max<int64_t>(c->head, (int64_t)c->log_cap * c->world), c->log_cap, c->W_cap, true).bytes,
+                    lrs_plan(c->log_cap, c->W_cap).bytes);
 }
 
 int fb_log_compact_shard_bytes(fb_ctx *c, int64_t *bytes) {
@@ -1903,7 +1905,7 @@ int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64
     a.bud = c->caps.clears == Clears::deferred ? c->bud : nullptr;
     {
         Timer t(c, "lr_flag");
-        launch_lr_flag(a, t.st());
+        launch_lr_flag(a, false, t.st());
     }
     {
         Timer t(c, "lc_scan");
@@ -1921,7 +1923,77 @@ int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64
     if (!n) return FB_OK;
     {
         Timer t(c, "lr_take");
-        launch_lr_take(a, t.st());
+        launch_lr_take(a, false, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    if (seq_out) HIPCHK(c, hipMemcpy(seq_out, a.seq_out, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (slot_out) HIPCHK(c, hipMemcpy(slot_out, a.slot_out, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return FB_OK;
+}
+
+// A rank's part of its group's reclaim ("A shard group's reclaim"): whether a
+// local entry goes depends on its own sequence against the bound and on its slot's record, epoch
+// and mask byte, all of which this rank holds -- so there is no exchange, and the call is
+// fb_log_reclaim's over the shard: count first, check the caller's room, only then take.  The
+// group agrees (every rank counts, cap = 0) before any rank takes.
+int fb_log_reclaim_shard(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out, int32_t *slot_out,
+                         int64_t cap, int64_t *n_reclaimed) {
+    if (!c) return FB_EINVAL;
+    if (below_seq < 0) return fail(c, FB_EINVAL, "below_seq %lld < 0", (long long)below_seq);
+    if ((seq_out || slot_out) && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
+    // (a dropped launch's in-place clears are taken back here: what its results named is live)
+    if (int rc_ = enter(c, life_gate_log_reclaim_shard(c->life, c->caps))) return rc_;
+    HIPCHK(c, hipSetDevice(c->device));
+    const LrPlan p = lrs_plan(c->head_local, c->W);
+    if (p.nt == 0 || c->W == 0) {  // (an empty shard, or a rank that owns no slot: nothing is launched)
+        if (n_reclaimed) *n_reclaimed = 0;
+        return FB_OK;
+    }
+    if (int rc_ = lc_scratch(c, p.bytes, lcs_full_bytes(c), 0)) return rc_;
+    char *const base = (char *)c->lc_mem;
+    // (the scratch is idle: every call that uses it waits for its launches before it returns,
+    // and no mark stands)
+    if (slot_mask) HIPCHK(c, hipMemcpy(base + p.mask, slot_mask, (size_t)c->W, hipMemcpyHostToDevice));
+    LrArgs a{};
+    a.log = c->log_slot;
+    a.B = std::min(below_seq, c->head);
+    a.W = c->W;
+    // (no sharded context commits lazily today: the test is kept for the day one does)
+    a.live_chk = c->life.stale ? 1 : 0;
+    a.reg = c->reg;
+    a.epoch = c->epoch;
+    a.mask = slot_mask ? (const uint8_t *)(base + p.mask) : nullptr;
+    a.t = LcTable{(unsigned long long *)(base + p.tab.bits), (uint32_t *)(base + p.tab.wrel), (uint32_t *)(base + p.tab.tcnt),
+                  (uint32_t *)(base + p.tab.tpre), p.nt};
+    a.seq_out = seq_out ? (int64_t *)(base + p.seq) : nullptr;
+    a.slot_out = slot_out ? (int32_t *)(base + p.slot) : nullptr;
+    a.bud = nullptr;  // (sharded contexts keep no per-slot budget)
+    a.seq = c->lseq;
+    a.n = c->head_local;
+    a.slot_base = c->slot_base;
+    {
+        Timer t(c, "lr_flag");
+        launch_lr_flag(a, true, t.st());
+    }
+    {
+        Timer t(c, "lc_scan");
+        launch_lc_scan(a.t, t.st());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, stream_wait(c));
+    uint32_t n = 0;
+    HIPCHK(c, hipMemcpy(&n, a.t.tpre + p.nt, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)n > c->head_local)
+        return fail(c, FB_EHIP, "device-reported reclaimed entries %u outside [0, %lld] (the log shard's entries)", n,
+                    (long long)c->head_local);
+    if (n_reclaimed) *n_reclaimed = (int64_t)n;
+    if ((seq_out || slot_out) && cap < (int64_t)n)
+        return fail(c, FB_EINVAL, "the outputs hold %lld entries, the call reclaims %u", (long long)cap, n);
+    if (!n) return FB_OK;
+    {
+        Timer t(c, "lr_take");
+        launch_lr_take(a, true, t.st());
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));

@@ -609,7 +609,8 @@ void launch_lc_scan(const LcTable &t, Stream st);
 void launch_lc_move(const LcArgs &a, bool shard, Stream st);
 void launch_lcs_mark(const LcArgs &a, Stream st);
 void launch_lcs_count(const LcArgs &a, Stream st);
-// fb_log_reclaim (one GPU; grids and the scratch regions: lr_plan, faasbal_layout.h).  Entry
+// fb_log_reclaim (grids and the scratch regions: lr_plan, faasbal_layout.h; a rank of a shard
+// group, fb_log_reclaim_shard: lrs_plan and the fields at the end).  On one GPU entry
 // q < B is reclaimed iff it is live by LcArgs' rule and (mask) mask[log[q]] != 0.
 struct LrArgs {
     int32_t *log;                // [head] the entries; the take pass writes -1
@@ -622,9 +623,17 @@ struct LrArgs {
     int64_t *seq_out;            // [reclaimed] ascending (null: not wanted)
     int32_t *slot_out;           // [reclaimed] (null: not wanted)
     int32_t *bud;                // in flight + free per slot (null: the context keeps none)
+    // the sharded variants only (last, so that the one-GPU kernels' argument offsets stay):
+    // fb_log_reclaim_shard over lrs_plan(n, W).  Local entry i is reclaimed iff seq[i] < B (B
+    // bounds sequences here, and t is over the n entries), it is live by LcArgs' rule on one of
+    // the rank's slots [slot_base, slot_base + W), and (mask) mask[log[i] - slot_base] != 0;
+    // seq_out takes seq[i], slot_out the global slot as logged.
+    const uint32_t *seq;         // [n] the entries' global sequences, ascending
+    int64_t n;                   // the shard's entries (head_local)
+    int slot_base;               // the rank's first global slot
 };
-void launch_lr_flag(const LrArgs &a, Stream st);
-void launch_lr_take(const LrArgs &a, Stream st);
+void launch_lr_flag(const LrArgs &a, bool shard, Stream st);
+void launch_lr_take(const LrArgs &a, bool shard, Stream st);
 // fb_pool_stats (grids, the partial rows' columns and the scratch regions: ps_plan,
 // faasbal_layout.h).  A slot is expired iff it holds a record and (now - hb) > tte (hb_chk:
 // heartbeat contexts; the tick's test); a log entry is live by LcArgs' rule.

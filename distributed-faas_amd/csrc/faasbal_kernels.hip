@@ -5267,40 +5267,65 @@ __global__ __launch_bounds__(kBS) void k_lc_move(LcArgs a) {
 // end test is the prefix test: every load is clamped to B - 1 (B <= head) and a bit at or
 // past B is 0, inside the last word and the last tile too; the epoch test compares the
 // entry's index, which the shorter count does not change.
+//
+// kShard, fb_log_reclaim_shard (lrs_plan): the same walk and table over the rank's n local
+// entries.  B bounds their sequences, not their indices, so the prefix test is seq[i] < B, on
+// the sequence loaded in the round of the mask gather (lc_batch<true, false> loads none; the
+// kChk form's own load of it is the same address and merges).  The entries name global slots:
+// the mask byte is gathered at the clamped rebased slot, and an entry is the rank's own where
+// its rebased slot is the clamped one.  The shard's sequences ascend, so a tile whose first
+// sequence is at or past B holds nothing: its wave leaves after that one load with a zero row
+// (and the take pass after the row's count), which keeps a deadline's short prefix on a long
+// shard at the prefix's traffic.
 // a tile's words of the reclaim bitmap, a wave: lane j < kLcWords gets word j (the other lanes 0)
-template <bool kChk, bool kMask>
+template <bool kShard, bool kChk, bool kMask>
 __device__ __forceinline__ unsigned long long lr_flag_tile(const LrArgs &a, int tile) {
     const int lane = lane_id();
-    const LcWalk w{a.log, nullptr, a.B, a.W, 0, a.reg, a.epoch};
+    const LcWalk w = kShard ? LcWalk{a.log, a.seq, a.n, a.W, a.slot_base, a.reg, a.epoch}
+                            : LcWalk{a.log, nullptr, a.B, a.W, 0, a.reg, a.epoch};
+    if (kShard) {
+        // (tile < nt: its first entry exists; one address for the wave, the branch scalar)
+        const uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.seq[(int64_t)tile * kLcTile]);
+        if ((int64_t)q0 >= a.B) return 0ull;
+    }
     unsigned long long mine = 0;
 #pragma unroll
     for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
         int32_t s[kLcBatch], sc[kLcBatch];
         bool live[kLcBatch];
         uint8_t mk[kLcBatch];  // the mask byte of the entry's (clamped) slot
-        lc_batch<false, kChk>(w, (int64_t)tile * kLcTile + lane, j0, s, sc, live, [&] {
+        uint32_t q[kLcBatch];  // (kShard) the entry's sequence
+        lc_batch<kShard, kChk>(w, (int64_t)tile * kLcTile + lane, j0, s, sc, live, [&] {
 #pragma unroll
-            for (int k = 0; k < kLcBatch; ++k) mk[k] = kMask ? a.mask[(uint32_t)sc[k]] : (uint8_t)1;
+            for (int k = 0; k < kLcBatch; ++k) {
+                mk[k] = kMask ? a.mask[(uint32_t)sc[k]] : (uint8_t)1;
+                if (kShard) {
+                    const int64_t i = (int64_t)tile * kLcTile + lane + (int64_t)(j0 + k) * 64;
+                    q[k] = a.seq[i < a.n ? i : a.n - 1];
+                }
+            }
         });
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
             // (a live entry's slot is its clamped one; a slot past the table names no mask byte)
-            const unsigned long long m = __ballot(live[k] && mk[k] && s[k] == sc[k]);
+            const unsigned long long m = kShard ? __ballot(live[k] && mk[k] && s[k] - a.slot_base == sc[k] && (int64_t)q[k] < a.B)
+                                                : __ballot(live[k] && mk[k] && s[k] == sc[k]);
             if (lane == j0 + k) mine = m;
         }
-        if (kChk || kMask) __builtin_amdgcn_sched_barrier(0);
+        if (kShard || kChk || kMask) __builtin_amdgcn_sched_barrier(0);
     }
     return mine;
 }
 
-// the table but for tpre, over the prefix's tiles; writes only the scratch
+// the table but for tpre, over the prefix's tiles (a shard: its local tiles); writes only the scratch
+template <bool kShard>
 __global__ __launch_bounds__(kBS) void k_lr_flag(LrArgs a) {
     prefetch_args(a);
     const int tile = (int)blockIdx.x * kWaves + wave_id();
     if (tile >= a.t.nt) return;  // (the whole wave)
     unsigned long long mine;
-    if (a.live_chk) mine = a.mask ? lr_flag_tile<true, true>(a, tile) : lr_flag_tile<true, false>(a, tile);
-    else mine = a.mask ? lr_flag_tile<false, true>(a, tile) : lr_flag_tile<false, false>(a, tile);
+    if (a.live_chk) mine = a.mask ? lr_flag_tile<kShard, true, true>(a, tile) : lr_flag_tile<kShard, true, false>(a, tile);
+    else mine = a.mask ? lr_flag_tile<kShard, false, true>(a, tile) : lr_flag_tile<kShard, false, false>(a, tile);
     lc_table_tile<true>(a.t, tile, mine);
 }
 
@@ -5312,36 +5337,44 @@ __global__ __launch_bounds__(kBS) void k_lr_flag(LrArgs a) {
 // count (a readfirstlane and a ballot per word decide).  Any other word goes a lane at a time:
 // its addresses differ, so there is nothing to serialise, and a sort to combine the partial
 // runs would cost more than the atomics it saves.
+// kShard: the sequence is seq[i], the slot the global one as logged, and there is no budget
+// (sharded contexts keep none); a tile without a set bit is left after its count's load.
+template <bool kShard>
 __global__ __launch_bounds__(kBS) void k_lr_take(LrArgs a) {
     prefetch_args(a);
     const int tile = (int)blockIdx.x * kWaves + wave_id();
     if (tile >= a.t.nt) return;  // (the whole wave)
+    if (kShard && __builtin_amdgcn_readfirstlane((int)a.t.tcnt[tile]) == 0) return;  // (the whole wave)
     const int lane = lane_id();
     const int64_t i0 = (int64_t)tile * kLcTile + lane;
+    const int64_t n = kShard ? a.n : a.B;  // the entries walked
     unsigned long long mine;
     uint32_t pre;
     lc_tile_words(a.t, tile, mine, pre);
     for (int j0 = 0; j0 < kLcWords; j0 += kLcBatch) {
         int32_t s[kLcBatch];
+        uint32_t q[kLcBatch];  // (kShard)
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
             const int64_t i = i0 + (int64_t)(j0 + k) * 64;
-            s[k] = a.log[i < a.B ? i : a.B - 1];
+            const int64_t ic = i < n ? i : n - 1;
+            s[k] = a.log[ic];
+            if (kShard) q[k] = a.seq[ic];
         }
 #pragma unroll
         for (int k = 0; k < kLcBatch; ++k) {
             const unsigned long long m = __shfl(mine, j0 + k, 64);
             const uint32_t p = (uint32_t)__shfl((int)pre, j0 + k, 64);
             if (!m) continue;  // (wave-uniform)
-            const bool set = (m >> lane) & 1ull;  // (a set bit: i < B, 0 <= s[k] < W)
+            const bool set = (m >> lane) & 1ull;  // (a set bit: i < n, the slot one of the table's)
             const int64_t i = i0 + (int64_t)(j0 + k) * 64;
             if (set) {
                 const int64_t o = (int64_t)p + popc_lt(m);
-                if (a.seq_out) a.seq_out[o] = i;
+                if (a.seq_out) a.seq_out[o] = kShard ? (int64_t)q[k] : i;
                 if (a.slot_out) a.slot_out[o] = s[k];
                 a.log[i] = -1;
             }
-            if (a.bud) {
+            if (!kShard && a.bud) {
                 const int first = __builtin_ctzll(m);
                 const int32_t s1 = __shfl(s[k], first, 64);
                 const bool one = __ballot(set && s[k] != s1) == 0ull;
@@ -5752,9 +5785,14 @@ void launch_lc_scan(const LcTable &t, Stream st) { lc_launch(k_lc_scan, kLcScanG
 void launch_lc_move(const LcArgs &a, bool shard, Stream st) {
     lc_launch(shard ? k_lc_move<true> : k_lc_move<false>, lc_plan_of(a, shard).move.grid(), a, st);
 }
-// (the grids of lr_plan(head, B, W) depend on B alone)
-void launch_lr_flag(const LrArgs &a, Stream st) { lc_launch(k_lr_flag, lr_plan(a.B, a.B, a.W).flag_grid, a, st); }
-void launch_lr_take(const LrArgs &a, Stream st) { lc_launch(k_lr_take, lr_plan(a.B, a.B, a.W).take_grid, a, st); }
+// (the grids of lr_plan(head, B, W) depend on B alone; a shard's, lrs_plan's, on its entries)
+static LrPlan lr_plan_of(const LrArgs &a, bool shard) { return shard ? lrs_plan(a.n, a.W) : lr_plan(a.B, a.B, a.W); }
+void launch_lr_flag(const LrArgs &a, bool shard, Stream st) {
+    lc_launch(shard ? k_lr_flag<true> : k_lr_flag<false>, lr_plan_of(a, shard).flag_grid, a, st);
+}
+void launch_lr_take(const LrArgs &a, bool shard, Stream st) {
+    lc_launch(shard ? k_lr_take<true> : k_lr_take<false>, lr_plan_of(a, shard).take_grid, a, st);
+}
 void launch_lcs_mark(const LcArgs &a, Stream st) { lc_launch(k_lcs_mark, lc_plan_of(a, true).mark_grid, a, st); }
 void launch_lcs_count(const LcArgs &a, Stream st) { lc_launch(k_lcs_count, lc_plan_of(a, true).count_grid, a, st); }
 void launch_ps_slots(const PsArgs &a, Stream st) {

@@ -367,7 +367,8 @@ inline LcPlan lcs_plan(int64_t head, int64_t head_local, int W, bool want_kept) 
 
 // ---------------------------------------------------------------------------------------
 // fb_log_reclaim: the compaction family's walk and table over the prefix [0, B) of a one-GPU
-// log, B = min(below_seq, head), in the compactions' scratch:
+// log, B = min(below_seq, head), in the compactions' scratch (a rank of a shard
+// group: lrs_plan below):
 //   k_lr_flag   a workgroup per four tiles of the prefix: the table's bitmap of the entries to
 //               reclaim (whole tiles: bits at or past B are 0), wrel and tcnt
 //   k_lc_scan   as it is: tpre; tpre[nt] is the count the host checks against the caller's cap
@@ -400,6 +401,13 @@ inline LrPlan lr_plan(int64_t head, int64_t below_seq, int W) {
     p.bytes = r.o;
     return p;
 }
+// fb_log_reclaim_shard, a rank of a shard group: the same three launches over the rank's
+// head_local entries, whose sequences B bounds (LrArgs: the prefix test is seq[i] < B, so how
+// many entries lie below B is not known before the walk).  The table is over all the local
+// tiles -- a tile past the bound costs its wave one load and a zero row -- and the two lists
+// hold head_local entries each, the count's bound.  That is the one-GPU plan of a log of
+// head_local entries walked whole (B here: the entries, not the caller's bound), stated so.
+inline LrPlan lrs_plan(int64_t head_local, int W) { return lr_plan(head_local, head_local, W); }
 
 // ---------------------------------------------------------------------------------------
 // fb_pool_stats: three launches, none of which writes anything but the scratch.

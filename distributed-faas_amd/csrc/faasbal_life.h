@@ -203,15 +203,16 @@ inline Gate life_gate_pool_stats_shard(const Life &l, const CtxCaps &k) {
 // fb_log_reclaim, live entries of workers that stay registered completed between ticks:
 // fb_pool_stats' gate -- the same refusals at every point of a tick, the same flush and undo --
 // with two refusals of its own.  A deque context has no liveness, so nothing to reclaim from.  A
-// sharded context's sequences are global across the ranks: a group form would take the shape
-// of fb_log_compact_shard_mark / _apply (mark, all-reduce, apply), which this is not.  It makes
+// sharded context's sequences are global across the ranks and its bound is the group's: the
+// rank's part is fb_log_reclaim_shard (below), which needs no mark / all-reduce / apply the way
+// fb_log_compact_shard_mark / _apply do, since it renumbers nothing.  It makes
 // no transition: the Life after a success is the Life before it (a window stays a window, a
 // stale log stale).  (No Call of its own, as fb_pool_stats_shard.)
 inline Gate life_gate_log_reclaim(const Life &l, const CtxCaps &k) {
     if (k.deque) return Gate{"fb_log_reclaim on a deque context: it keeps no liveness, nothing is in flight on a record", 0u};
     if (k.sharded)
-        return Gate{"fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (a group form "
-                    "would follow fb_log_compact_shard_mark / _apply)",
+        return Gate{"fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (unlike "
+                    "fb_log_compact_shard_mark / _apply it needs no exchange): use fb_log_reclaim_shard",
                     0u};
     Gate g = life_gate(l, k, Call::pool_stats);
     if (g.refuse) {
@@ -220,6 +221,24 @@ inline Gate life_gate_log_reclaim(const Life &l, const CtxCaps &k) {
         if (l.staged) return Gate{"fb_log_reclaim with staged events pending: launch and commit their tick first", g.duties};
         if (life_waited(l)) return Gate{"fb_log_reclaim between a tick's wait and its commit: fb_tick_commit first", g.duties};
         return Gate{"fb_log_reclaim with a tick launched: fb_tick_wait and fb_tick_commit first", g.duties};
+    }
+    return g;
+}
+
+// fb_log_reclaim_shard, a rank's part of its group's reclaim: built from fb_pool_stats' gate the
+// way fb_pool_stats_shard's is -- the sharded refusal lifted, the same refusals at every point
+// of a tick (under this call's name), the same flush and undo -- and a refusal of its own where
+// fb_log_reclaim answers.  The undo comes first: a launch the wait dropped has its in-place
+// clears taken back, so the entries its results named count as live.  No transition.
+inline Gate life_gate_log_reclaim_shard(const Life &l, const CtxCaps &k) {
+    if (!k.sharded)
+        return Gate{"fb_log_reclaim_shard on a one-GPU context: use fb_log_reclaim", l.cm_pending ? (unsigned)kFlush : 0u};
+    const Gate g = life_gate_pool_stats_shard(l, k);
+    if (g.refuse) {
+        if (l.marked) return g;  // (kLifeMarkedRefusal)
+        if (l.staged) return Gate{"fb_log_reclaim_shard with staged events pending: launch and commit their tick first", g.duties};
+        if (life_waited(l)) return Gate{"fb_log_reclaim_shard between a tick's wait and its commit: fb_tick_commit first", g.duties};
+        return Gate{"fb_log_reclaim_shard with a tick launched: fb_tick_wait and fb_tick_commit first", g.duties};
     }
     return g;
 }

@@ -31,7 +31,7 @@ EXPORTS = ("fb_create", "fb_destroy", "fb_last_error", "fb_load_state", "fb_read
            "fb_set_round_hint", "fb_set_full_assign", "fb_timing_gate", "fb_timing_span",
            "fb_timing_mark", "fb_log_compact", "fb_pool_stats", "fb_pool_stats_shard", "fb_pool_merge",
            "fb_log_compact_shard_bytes", "fb_log_compact_shard_mark", "fb_log_compact_shard_apply",
-           "fb_log_compact_shard_cancel", "fb_log_reclaim")
+           "fb_log_compact_shard_cancel", "fb_log_reclaim", "fb_log_reclaim_shard")
 
 
 class TickResult(C.Structure):
@@ -148,6 +148,7 @@ def load(path=None):
         "fb_log_compact_shard_apply": (C.c_int, [_P, i64, _P, i64, C.POINTER(i64)]),
         "fb_log_compact_shard_cancel": (C.c_int, [_P]),
         "fb_log_reclaim": (C.c_int, [_P, i64, _P, _P, _P, i64, C.POINTER(i64)]),
+        "fb_log_reclaim_shard": (C.c_int, [_P, i64, _P, _P, _P, i64, C.POINTER(i64)]),
         "fb_pool_stats": (C.c_int, [_P, dbl, dbl, _P, C.c_int32, C.POINTER(PoolSummary)]),
         "fb_pool_stats_shard": (C.c_int, [_P, dbl, dbl, _P, C.c_int32, C.POINTER(PoolSummary), C.POINTER(i64)]),
         "fb_pool_merge": (C.c_int, [_P, C.POINTER(PoolSummary), C.POINTER(i64), C.c_int32, C.POINTER(PoolSummary)]),

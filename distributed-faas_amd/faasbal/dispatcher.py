@@ -130,8 +130,9 @@ class GpuPushDispatcher:
         self.task_timeout = None if task_timeout is None else float(task_timeout)
         self.max_attempts = None if max_attempts is None else int(max_attempts)
         if self.task_timeout is not None and not callable(getattr(self.balancer, "reclaim", None)):
-            raise FaasbalError(FB_ESTATE, "task_timeout needs a balancer with reclaim (fb_log_reclaim): one GPU; "
-                                          "a shard group has none yet")
+            raise FaasbalError(FB_ESTATE, "task_timeout needs a balancer with reclaim (fb_log_reclaim; a shard "
+                                          "group's: fb_log_reclaim_shard): this one has none -- a group whose "
+                                          "rank balancers lack reclaim_part")
         self.reclaimed = 0                             # tasks taken back from live workers
         self.timed_out_failed = 0                      # ... of which recorded FAILED (max_attempts)
         self._reset_host()
@@ -366,7 +367,8 @@ class GpuPushDispatcher:
         workers that are gone.  Returns the task ids."""
         device = getattr(self.balancer, "reclaim", None)
         if not callable(device):
-            raise FaasbalError(FB_ESTATE, "this balancer has no reclaim (fb_log_reclaim): one GPU only")
+            raise FaasbalError(FB_ESTATE, "this balancer has no reclaim (fb_log_reclaim, fb_log_reclaim_shard): a shard group "
+                                         "whose rank balancers lack reclaim_part")
         slots = [self.slot_of[w] for w in worker_ids if w in self.slot_of]
         if not slots:
             return []

@@ -87,9 +87,43 @@ class ShardedBalancer(GpuBalancer):
     # fb_pool_stats too: a rank cannot answer for the group.  Its part is pool_stats_part;
     # ShardGroup.pool_stats gathers and merges the ranks' parts
     pool_stats = None
-    # fb_log_reclaim as well (global sequences): a group form would follow the compaction's
-    # mark / all-reduce / apply; until then a shard group has no reclaim
+    # fb_log_reclaim as well (global sequences, and the bound is the group's).  Its part is
+    # reclaim_part; ShardGroup.reclaim has every rank count before any rank takes and merges
+    # the ranks' lists
     reclaim = None
+
+    def reclaim_part(self, below_seq=None, slots=None, count_only=False):
+        """fb_log_reclaim_shard: this rank's part of the group's reclaim -- every live entry
+        of its log shard with a global sequence below ``below_seq`` (None: the head) on one of
+        ``slots`` (GLOBAL slots, None: all; those outside this rank's range are another
+        rank's and are dropped here) is completed on the device.  Returns dict(n, seq, slot):
+        the global sequences (int64, ascending) and the global slot each was on (int32).
+        ``count_only``: the call with outputs and no room -- dict(n, None, None), and nothing
+        has changed; it makes every refusal the taking call would make.  Between ticks."""
+        below = (1 << 62) if below_seq is None else int(below_seq)
+        mask = None
+        if slots is not None:
+            mask = np.zeros(max(self.n_local, 1), np.uint8)
+            idx = np.asarray(slots if isinstance(slots, np.ndarray) else list(slots), np.int64).reshape(-1) - self.base
+            mask[idx[(idx >= 0) & (idx < self.n_local)]] = 1
+        mp = None if mask is None else mask.ctypes.data_as(C.c_void_p)
+        n = C.c_int64()
+        cap = 0 if count_only else 256
+        while True:
+            seq = np.zeros(max(cap, 1), np.int64)
+            slot = np.zeros(max(cap, 1), np.int32)
+            n.value = -1
+            rc = self.lib.fb_log_reclaim_shard(self.h, below, mp, seq.ctypes.data_as(C.c_void_p),
+                                               slot.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+            if rc == _lib.FB_EINVAL and n.value > cap:  # nothing changed: the count, or come back with room
+                if count_only:
+                    return {"n": n.value, "seq": None, "slot": None}
+                cap = n.value
+                continue
+            self._chk(rc)
+            if count_only:
+                return {"n": n.value, "seq": None, "slot": None}
+            return {"n": n.value, "seq": seq[: n.value], "slot": slot[: n.value]}
 
     def pool_stats_part(self, now, tte, age_edges=()):
         """fb_pool_stats_shard: this rank's part of the group's pool summary as
@@ -299,6 +333,9 @@ class ShardGroup:
         # ... or without the parts of a compaction: GpuPushDispatcher.compact_log takes its host path
         if not all(callable(getattr(b, m, None)) for b in rank_balancers for m in COMPACT_PARTS):
             self.compact_log = None
+        # ... or without a part of a reclaim: GpuPushDispatcher refuses task_timeout over the group
+        if not all(callable(getattr(b, "reclaim_part", None)) for b in rank_balancers):
+            self.reclaim = None
 
     def _each(self, op, **kw):  # -> list of per-rank results, rank order
         raise NotImplementedError
@@ -326,6 +363,25 @@ class ShardGroup:
         when the group's total differs, or when a rank could not mark."""
         out = self._each("compact", expect=-1 if expect is None else int(expect), want_kept=bool(want_kept))[0]
         return {"n_kept": out["n_kept"], "kept": out["kept"]}
+
+    def reclaim(self, below_seq=None, slots=None):
+        """Take live log entries back from workers that stay registered, where the shards
+        live (``GpuBalancer.reclaim``'s contract: dict(n, seq, slot), ``seq`` int64 ascending
+        across the whole group, ``slot`` the global slot each was on, int32; ``slots`` global,
+        None: all).  A reclaim renumbers nothing, so each rank decides about its own entries
+        and the device needs no collective; the group's part is agreement -- every rank
+        counts first, which is every refusal it would make, and only when all of them can do
+        the ranks take: a rank that refuses (FB_ESTATE: a tick not committed there, staged
+        events, a marked compaction) leaves every shard as it was, and its code is raised.
+        The ranks' lists are merged by sequence (they are disjoint).  Between ticks."""
+        idx = None
+        if slots is not None:
+            idx = np.asarray(slots if isinstance(slots, np.ndarray) else list(slots), np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= self.n_workers_global):
+                raise ValueError("slots outside [0, %d)" % self.n_workers_global)
+            idx = idx.astype(np.int32)
+        parts = self._each("reclaim", below_seq=(1 << 62) if below_seq is None else int(below_seq), slots=idx)
+        return merge_reclaimed(parts)
 
     def load_state(self, reg, free, hb, epoch=None, queue=(), log=()):
         W = len(reg)
@@ -365,6 +421,22 @@ class ShardGroup:
         pass
 
 
+def merge_reclaimed(parts):
+    """The group's dict(n, seq, slot) from the ranks' reclaim_part results: one list ascending
+    by sequence (the ranks' sequences are disjoint, each rank's ascending already)."""
+    seq = np.concatenate([np.asarray(p["seq"], np.int64) for p in parts]) if parts else np.zeros(0, np.int64)
+    slot = np.concatenate([np.asarray(p["slot"], np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    order = np.argsort(seq, kind="stable")
+    return {"n": int(len(seq)), "seq": seq[order], "slot": slot[order]}
+
+
+def _guarded(f, *a):
+    try:
+        return (True, f(*a))
+    except Exception as e:  # noqa: BLE001 -- the group raises it once every rank has answered
+        return (False, _failure(e))
+
+
 def serve_op(bal, op, kw, allreduce=None, commit=True):
     """One group operation on this rank's balancer (every rank runs the same op).
     ``commit=False`` leaves a tick / purge waited but uncommitted (DistShardGroup
@@ -385,6 +457,12 @@ def serve_op(bal, op, kw, allreduce=None, commit=True):
     if op == "compact":  # (a collective of its own: mark, reduce, agree, apply or cancel)
         import torch.distributed as dist
         out, bad = _compact_rank(dist, _dev(dist), bal, kw, allreduce)
+        if bad is not None:
+            _raise_bad(op, bad)
+        return out
+    if op == "reclaim":  # (an agreement of its own: count, agree, take)
+        import torch.distributed as dist
+        out, bad = _reclaim_rank(dist, _dev(dist), bal, kw)
         if bad is not None:
             _raise_bad(op, bad)
         return out
@@ -473,6 +551,46 @@ def _compact_rank(dist, dev, bal, kw, allreduce=None):
     return out, bad
 
 
+def _reclaim_rank(dist, dev, bal, kw):
+    """A group reclaim on this rank (every rank runs it): count, one header all-gather of the
+    ranks' ok flags and counts -- when a rank refused nothing has changed anywhere, and no rank
+    takes --, take, a second header (a take that fails now is the rank's own runtime error),
+    then the lists to rank 0 as one padded byte tensor per rank, 12 bytes per entry (the
+    sequences, then the slots).  Returns (rank 0: the ranks' dict(n, seq, slot) in rank order;
+    the others: None, the first failure or None)."""
+    import torch
+    rank, world = dist.get_rank(), dist.get_world_size()
+    cnt = _guarded(bal.reclaim_part, kw["below_seq"], kw["slots"], True)
+    flags = _gather_flags(dist, dev, cnt[0], None if cnt[0] else cnt[1], cnt[1]["n"] if cnt[0] else 0)
+    bad = next((f[1] for f in flags if not f[0]), None)
+    if bad is not None:
+        return None, bad
+    done = _guarded(bal.reclaim_part, kw["below_seq"], kw["slots"])
+    if done[0] and done[1]["n"] != flags[rank][1]:
+        done = (False, (_lib.FB_ESTATE, "rank %d counted %d entries to reclaim and took %d"
+                        % (rank, flags[rank][1], done[1]["n"])))
+    after = _gather_flags(dist, dev, done[0], None if done[0] else done[1])
+    bad = next((f[1] for f in after if not f[0]), None)
+    if bad is not None:
+        return None, bad
+    counts = [int(f[1]) for f in flags]
+    mx = max(counts[1:], default=0)
+    parts = [done[1]] + [dict(n=0, seq=np.zeros(0, np.int64), slot=np.zeros(0, np.int32)) for _ in range(world - 1)]
+    if mx > 0:
+        mine = torch.zeros(12 * mx, dtype=torch.uint8)
+        if rank != 0 and counts[rank]:
+            payload = np.concatenate([np.ascontiguousarray(done[1]["seq"], np.int64).view(np.uint8),
+                                      np.ascontiguousarray(done[1]["slot"], np.int32).view(np.uint8)])
+            mine[:len(payload)] = torch.from_numpy(payload)
+        bufs = [torch.zeros(12 * mx, dtype=torch.uint8, device=dev) for _ in range(world)] if rank == 0 else None
+        dist.gather(mine.to(dev), bufs, dst=0)
+        if rank == 0:
+            for i in range(1, world):
+                b, n = bufs[i].cpu().numpy(), counts[i]
+                parts[i] = dict(n=n, seq=b[:8 * n].view(np.int64).copy(), slot=b[8 * n:12 * n].view(np.int32).copy())
+    return (parts if rank == 0 else None), None
+
+
 def _serve_guarded(bal, op, kw):
     """serve_op on this rank, its failure returned instead of raised: every rank must
     still reach the group's gather (a rank that skipped it would leave the others
@@ -508,7 +626,14 @@ def _settle(bal, op, outs):
 # in the event count's word, whether rank 0 wants the kept list in the tasks' word.  Its
 # payload is the live bitmap, all-reduced in place like a tick's exchange; one fixed header
 # per rank (ok flag, code, live count) is all-gathered before the apply and one after it.
-_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6, "compact": 7}
+# A reclaim ("reclaim") travels as tensors as well, since with task_timeout it can run at the
+# top of every tick: the call header carries below_seq in the event count's word and the number
+# of slots in the tasks' word (-1: no mask), the global slots follow as one int32 tensor when
+# there are any; one fixed header per rank (ok flag, code, count) is all-gathered after the
+# count step and one after the take, and the lists come back as one padded byte tensor per rank
+# gathered to rank 0, 12 bytes per entry (the int64 sequences, then the int32 slots); pickled
+# messages follow only when a rank failed.
+_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6, "compact": 7, "reclaim": 8}
 _OP_NAMES = {v: k for k, v in _OP_CODES.items()}
 _HDR = 8  # int64 words of the call header / the per-rank result header
 _PS_WORDS = C.sizeof(_lib.PoolSummary) // 8  # fb_pool_summary's words (SCALARS' order, then HISTS')
@@ -573,6 +698,9 @@ def _bcast_call(dist, dev, op, kw):
     elif op == "compact":  # (the header is the whole call)
         h[1] = int(kw["expect"])
         h[2] = 1 if kw["want_kept"] else 0
+    elif op == "reclaim":
+        h[1] = int(kw["below_seq"])
+        h[2] = -1 if kw["slots"] is None else len(kw["slots"])
     dist.broadcast(h.to(dev), src=0)
     if op in ("tick", "purge"):
         if int(h[1]):
@@ -580,6 +708,9 @@ def _bcast_call(dist, dev, op, kw):
     elif op == "stats":
         if int(h[1]):
             dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["age_edges"], np.float64)).to(dev), src=0)
+    elif op == "reclaim":
+        if int(h[2]) > 0:
+            dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["slots"], np.int32)).to(dev), src=0)
     elif op not in ("stop", "compact"):
         dist.broadcast_object_list([kw], src=0)
 
@@ -593,6 +724,14 @@ def _recv_call(dist, dev):
     op = _OP_NAMES[int(h[0])]
     if op == "compact":
         return op, dict(expect=int(h[1]), want_kept=bool(h[2]))
+    if op == "reclaim":
+        slots = None
+        if int(h[2]) >= 0:
+            slots = torch.zeros(int(h[2]), dtype=torch.int32, device=dev)
+            if int(h[2]):
+                dist.broadcast(slots, src=0)
+            slots = slots.cpu().numpy()
+        return op, dict(below_seq=int(h[1]), slots=slots)
     if op == "stats":
         edges = torch.zeros(int(h[1]), dtype=torch.float64, device=dev)
         if int(h[1]):
@@ -717,8 +856,9 @@ class DistShardGroup(ShardGroup):
     all-reduce over the group's backend (RCCL over xGMI for ``nccl``) -- and the
     per-rank results come back to rank 0.  Ticks and purges travel as tensors (the
     event batch in one broadcast, the results in one gather) and so do pool summaries (one
-    fixed record per rank) and log compactions (the live bitmap all-reduced in place, a fixed
-    header per rank); loads and state reads as pickled objects."""
+    fixed record per rank), log compactions (the live bitmap all-reduced in place, a fixed
+    header per rank) and reclaims (a fixed header per rank, the lists in one gather); loads and
+    state reads as pickled objects."""
 
     def __init__(self, balancer, n_workers):
         super().__init__(n_workers, (balancer,))
@@ -737,6 +877,11 @@ class DistShardGroup(ShardGroup):
             if bad is not None:
                 _raise_bad(op, bad)
             return [out]
+        if op == "reclaim":
+            parts, bad = _reclaim_rank(self.dist, self.dev, self.bal, kw)
+            if bad is not None:
+                _raise_bad(op, bad)
+            return parts
         guarded = _serve_guarded(self.bal, op, kw)
         outs = _gather(self.dist, self.dev, op, guarded)
         bad = _settle(self.bal, op, outs)
@@ -759,6 +904,9 @@ def serve_shard(balancer):
         if op == "compact":
             _compact_rank(dist, dev, balancer, kw)  # rank 0 raises a failure; this rank keeps serving
             continue
+        if op == "reclaim":
+            _reclaim_rank(dist, dev, balancer, kw)  # (likewise: a refused reclaim changed nothing)
+            continue
         guarded = _serve_guarded(balancer, op, kw)
         outs = _gather(dist, dev, op, guarded)
         _settle(balancer, op, outs)  # rank 0 raises a failure; this rank keeps serving
@@ -779,7 +927,18 @@ class LocalShardGroup(ShardGroup):
             return self._collective(op, kw)
         if op == "compact":
             return self._compact(kw)
+        if op == "reclaim":
+            return self._reclaim(kw)
         return [serve_op(b, op, kw) for b in self.bals]
+
+    def _reclaim(self, kw):
+        # every rank counts -- every refusal a rank would make, with nothing changed anywhere --
+        # and only when all of them can do the ranks take
+        counts = [_guarded(b.reclaim_part, kw["below_seq"], kw["slots"], True) for b in self.bals]
+        bad = next((c[1] for c in counts if not c[0]), None)
+        if bad is not None:
+            _raise_bad("reclaim", bad)
+        return [b.reclaim_part(kw["below_seq"], kw["slots"]) for b in self.bals]
 
     def _compact(self, kw):
         # mark on every rank, the bitmaps summed on the device (as _collective_once sums the

@@ -239,12 +239,38 @@ int fb_log_compact_shard_cancel(fb_ctx *ctx);
  * cap < the count, FB_EINVAL, nothing changes and *n_reclaimed holds the count to come back
  * with.  below_seq < 0: FB_EINVAL.
  * FB_ESTATE: a deque context (no liveness), a sharded context (its sequences are global across
- * ranks; a group form would follow fb_log_compact_shard_mark / _apply), and out of order, as
+ * ranks: a rank's part of its group's reclaim is fb_log_reclaim_shard), and out of order, as
  * fb_pool_stats.
  * Answers what the reference leaves open, which keeps no log: "if something happens with the
  * worker, the task is gone", "if a worker ressucitates" (README.md:263-264). */
 int fb_log_reclaim(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out,
                    int32_t *slot_out, int64_t cap, int64_t *n_reclaimed);
+
+/* Sharded contexts, between ticks: this rank's part of its group's reclaim.
+ * Unlike a compaction a reclaim renumbers nothing, so whether an entry goes depends only on what
+ * the rank that owns it holds: there is no exchange buffer and no collective on the device.  Let
+ * B = min(below_seq, the global log_head).  Local entry i is reclaimed iff log_seq[i] < B, it is
+ * live by fb_load_shard's rule (log_slot[i] >= 0 on one of the rank's own slots, and, where
+ * lazily kept entries may be in the log, its slot holds a record and log_seq[i] >= epoch[slot]),
+ * and slot_mask == NULL or slot_mask[log_slot[i] - slot_base] != 0 (slot_mask: this rank's
+ * n_workers host bytes, indexed locally like every array of fb_load_shard).
+ * Effect: log_slot[i] = -1 for every reclaimed entry, and nothing else: log_seq, the local
+ * length, the global head, records, epochs, free counts, the replicated queue, the round hint,
+ * the bound exchange buffer and the tick pipeline stay (sharded contexts keep no in-flight
+ * counts).  The state afterwards is the one fb_load_shard installs from the rank's read-back
+ * arrays with those entries at -1.
+ * seq_out / slot_out (either or both may be NULL; cap entries each): the reclaimed entries'
+ * global sequences, ascending, and the global slot each was on.  cap and *n_reclaimed are
+ * fb_log_reclaim's: the count is set as soon as it is known, before anything but scratch is
+ * written; with an output given and cap < the count, FB_EINVAL, nothing changes and the count
+ * comes back.  A group calls every rank with cap = 0 first -- a count, and every refusal a rank
+ * has to make, before any rank has taken anything -- and only then with room.
+ * below_seq < 0: FB_EINVAL.  FB_ESTATE: a one-GPU context (use fb_log_reclaim), between a
+ * compaction's mark and its apply or cancel, and out of order, as fb_pool_stats_shard
+ * (DESIGN.md §5f); a launch that fb_tick_wait dropped has its in-place clears taken back first,
+ * so the entries its results named count as live. */
+int fb_log_reclaim_shard(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out,
+                         int32_t *slot_out, int64_t cap, int64_t *n_reclaimed);
 
 /* One-GPU contexts (heartbeat and deque), between ticks: a summary of the committed worker pool
  * at the clock `now`, computed where the state lives (three launches, a few hundred bytes back;

@@ -13,6 +13,14 @@ starts from the same loaded state (the load is not timed) and the two legs' resu
 and in-flight counts are compared once per case.  Medians go to the JSON.
 
     python tools/reclaim_probe.py --out profiles/reclaim_probe.json
+
+With ``--world N[,N..]`` the same cases run on a shard group instead (LocalShardGroup: N rank
+contexts on this one GPU, fb_log_reclaim_shard behind ShardGroup.reclaim -- every rank counts,
+then every rank takes) against the group's host path (ShardGroup.read_state, the rule in numpy,
+ShardGroup.load_state); the kernels' times are per rank and launch (the mean and the maximum
+over the ranks).  A group's collectives across GPUs are not in these numbers.
+
+    python tools/reclaim_probe.py --world 2,8 --out profiles/reclaim_shard_probe.json
 """
 import argparse
 import json
@@ -59,6 +67,64 @@ def med(x):
     return float(np.median(x))
 
 
+class _Group:
+    """A LocalShardGroup behind the calls run_case makes of a GpuBalancer.  The untimed loads
+    install shards split once (fb_load_shard, as ShardedBalancer.load does)."""
+
+    def __init__(self, world, W, head):
+        from faasbal.sharded import LocalShardGroup
+        self.g = LocalShardGroup(world, W, 2 * head // world + 65536, max_events=64)
+        self.world, self.shards = world, None
+
+    def load(self, st):
+        from faasbal.balancer import _p
+        from faasbal.sharded import split_state
+        if self.shards is None or self.shards[0] is not st:
+            q = np.asarray(st["queue"], np.int64)
+            hint = max(1, min(int(np.asarray(st["free"])[q].max()) if len(q) else 1, 1 << 30))
+            self.shards = (st, [split_state(st, self.world, r) for r in range(self.world)], hint)
+        for b, sh in zip(self.g.bals, self.shards[1]):
+            b._chk(b.lib.fb_load_shard(b.h, sh["base"], sh["n"], _p(sh["reg"]), _p(sh["free"]), _p(sh["hb"]),
+                                       _p(sh["epoch"]), _p(sh["queue"]), len(sh["queue"]), _p(sh["log_slot"]),
+                                       _p(sh["log_seq"]), len(sh["log_slot"]), sh["log_head"]))
+            b._chk(b.lib.fb_set_round_hint(b.h, self.shards[2]))
+            b.n_workers = sh["n"]
+
+    def sync(self):
+        for b in self.g.bals:
+            b.sync()
+
+    def reclaim(self, below, slots):
+        return self.g.reclaim(below, slots)
+
+    def read_state(self, with_log=True):
+        return self.g.read_state(with_log)
+
+    def load_state(self, *a):
+        return self.g.load_state(*a)
+
+    def inflight(self):  # (sharded contexts keep no per-slot counts)
+        return np.zeros(0, np.uint32)
+
+    def timing_enable(self, on=True):
+        for b in self.g.bals:
+            b.timing_enable(on)
+
+    def timing_read(self):
+        """Per kernel: (the mean over the ranks of a rank's time per launch, 1), and under
+        ``<name>.max`` the slowest rank's."""
+        per = {}
+        for b in self.g.bals:
+            for k, (ms, cnt) in b.timing_read().items():
+                per.setdefault(k, []).append(ms / max(cnt, 1))
+        out = {k: (float(np.mean(v)), 1) for k, v in per.items()}
+        out.update({k + ".max": (float(np.max(v)), 1) for k, v in per.items()})
+        return out
+
+    def close(self):
+        self.g.close()
+
+
 def run_case(g, st, below, slots, reps):
     mask = None
     if slots is not None:
@@ -101,22 +167,26 @@ def main():
     ap.add_argument("--sizes", default="1M,16M")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--world", default=None, help="shard groups of N ranks on this GPU, e.g. 2,8 (default: one GPU)")
     a = ap.parse_args()
     res = {}
+    worlds = [None] if a.world is None else [int(w) for w in a.world.split(",")]
     for name in a.sizes.split(","):
         sz = SIZES[name]
         st = make_state(sz["head"], sz["W"])
-        g = GpuBalancer(sz["W"], sz["head"] + 4096, max_events=64)
-        even = np.arange(0, sz["W"], 2)
-        for frac in FRACTIONS:
-            for masked in (False, True):
-                # a mask of every other slot halves what a prefix holds: twice the prefix for the same count
-                below = int(sz["head"] * frac * (2 if masked else 1))
-                key = "%s_%g%s" % (name, frac, "_mask" if masked else "")
-                res[key] = dict(head=sz["head"], W=sz["W"], below_seq=below, masked=masked,
-                                **run_case(g, st, below, even if masked else None, a.reps))
-                print(key, json.dumps(res[key]), flush=True)
-        g.close()
+        for world in worlds:
+            g = GpuBalancer(sz["W"], sz["head"] + 4096, max_events=64) if world is None else _Group(world, sz["W"], sz["head"])
+            even = np.arange(0, sz["W"], 2)
+            for frac in FRACTIONS:
+                for masked in (False, True):
+                    # a mask of every other slot halves what a prefix holds: twice the prefix for the same count
+                    below = int(sz["head"] * frac * (2 if masked else 1))
+                    key = "%s_%g%s%s" % (name, frac, "_mask" if masked else "", "" if world is None else "_N%d" % world)
+                    res[key] = dict(head=sz["head"], W=sz["W"], below_seq=below, masked=masked,
+                                    **({} if world is None else {"world": world}),
+                                    **run_case(g, st, below, even if masked else None, a.reps))
+                    print(key, json.dumps(res[key]), flush=True)
+            g.close()
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
