@@ -659,7 +659,8 @@ int log_undo(fb_ctx *c) {
 }
 
 // The top of every entry point: life_gate's refusal, or the duties it names, in order.
-int enter(fb_ctx *c, const Gate &g) {
+int enter(fb_ctx *c, Call call) {
+    const Gate g = life_gate(c->life, c->caps, call);
     if (g.duties & kFlush)
         if (int rc_ = flush_commit(c)) return rc_;
     if (g.refuse) return fail(c, FB_ESTATE, "%s", g.refuse);
@@ -668,7 +669,6 @@ int enter(fb_ctx *c, const Gate &g) {
     if (g.duties & kUndoSync) HIPCHK(c, stream_wait(c));
     return FB_OK;
 }
-int enter(fb_ctx *c, Call call) { return enter(c, life_gate(c->life, c->caps, call)); }
 
 // Whether the tick about to launch (c->l_*) runs as a window tick: plan_window's rules on
 // this context's state; c->l_nchW, the window chunks it scans.
@@ -1644,29 +1644,45 @@ int fb_read_inflight(fb_ctx *c, uint32_t *inflight) {
     return FB_OK;
 }
 
-// The compactions' scratch, one allocation for fb_log_compact and a shard
-// group's two halves: sized for this log (`need` bytes), doubling, never beyond a full one
-// (`full`); `keep` bytes of it (a mark's local table) survive a growth.
-static int lc_scratch(fb_ctx *c, size_t need, size_t full, size_t keep) {
-    if (need <= c->lc_cap) return FB_OK;
-    const size_t want = std::max(need, std::min(2 * c->lc_cap, full));
+// A maintenance call's device scratch (`what`, for the messages), made on first use: sized for
+// this state (`need` bytes), doubling, never beyond a full one (`full`); `keep` bytes of the
+// old one survive a growth.  The stream is idle before the old one goes.
+static int scratch_grow(fb_ctx *c, const char *what, void *&mem, size_t &cap, size_t need, size_t full, size_t keep) {
+    if (need <= cap) return FB_OK;
+    const size_t want = std::max(need, std::min(2 * cap, full));
     HIPCHK(c, stream_wait(c));
     void *m = nullptr;
     const hipError_t e = hipMalloc(&m, want);
-    if (e != hipSuccess)
-        return fail(c, FB_ENOMEM, "hipMalloc(compaction scratch %zu B) failed: %s", want, hipGetErrorString(e));
-    if (c->lc_mem) {
+    if (e != hipSuccess) return fail(c, FB_ENOMEM, "hipMalloc(%s %zu B) failed: %s", what, want, hipGetErrorString(e));
+    if (mem) {
         if (keep) {
-            const hipError_t ce = hipMemcpy(m, c->lc_mem, keep, hipMemcpyDeviceToDevice);
+            const hipError_t ce = hipMemcpy(m, mem, keep, hipMemcpyDeviceToDevice);
             if (ce != hipSuccess) {
                 hipFree(m);
-                return fail(c, FB_EHIP, "hipMemcpy(compaction scratch) failed: %s", hipGetErrorString(ce));
+                return fail(c, FB_EHIP, "hipMemcpy(%s) failed: %s", what, hipGetErrorString(ce));
             }
         }
-        hipFree(c->lc_mem);
+        hipFree(mem);
     }
-    c->lc_mem = m;
-    c->lc_cap = want;
+    mem = m;
+    cap = want;
+    return FB_OK;
+}
+// The compactions' scratch, one allocation for fb_log_compact, a shard group's
+// two halves (`keep`: a mark's local table) and the reclaims.
+static int lc_scratch(fb_ctx *c, size_t need, size_t full, size_t keep) {
+    return scratch_grow(c, "compaction scratch", c->lc_mem, c->lc_cap, need, full, keep);
+}
+static LcTable lc_table(char *base, const LcTableAt &t, int nt) {
+    return LcTable{(unsigned long long *)(base + t.bits), (uint32_t *)(base + t.wrel), (uint32_t *)(base + t.tcnt),
+                   (uint32_t *)(base + t.tpre), nt};
+}
+// A count the device wrote (after stream_wait), checked before it is used or handed out: FB_EHIP
+// when it is beyond `bound`, which `of` names.
+static int read_count(fb_ctx *c, const uint32_t *dev, const char *noun, int64_t bound, const char *of, uint32_t *n) {
+    HIPCHK(c, hipMemcpy(n, dev, 4, hipMemcpyDeviceToHost));
+    if ((int64_t)*n > bound)
+        return fail(c, FB_EHIP, "device-reported %s %u outside [0, %lld] (%s)", noun, *n, (long long)bound, of);
     return FB_OK;
 }
 
@@ -1674,10 +1690,6 @@ static int lc_scratch(fb_ctx *c, size_t need, size_t full, size_t keep) {
 // caller's exchange buffer; on one GPU the log's index is its sequence, and the tables are one.
 static LcArgs lc_args(fb_ctx *c, const LcPlan &p, bool want_kept) {
     char *const base = (char *)c->lc_mem;
-    const auto table = [base](const LcTableAt &t, int nt) {
-        return LcTable{(unsigned long long *)(base + t.bits), (uint32_t *)(base + t.wrel), (uint32_t *)(base + t.tcnt),
-                       (uint32_t *)(base + t.tpre), nt};
-    };
     LcArgs a{};
     a.log = c->log_slot;
     a.seq = c->shard ? c->lseq : nullptr;
@@ -1690,8 +1702,8 @@ static LcArgs lc_args(fb_ctx *c, const LcPlan &p, bool want_kept) {
     a.want_kept = want_kept ? 1 : 0;
     a.reg = c->reg;
     a.epoch = c->epoch;
-    a.loc = table(p.loc, p.ntl);
-    a.glob = table(p.glob, p.ntg);
+    a.loc = lc_table(base, p.loc, p.ntl);
+    a.glob = lc_table(base, p.glob, p.ntg);
     if (c->shard) a.glob.bits = (unsigned long long *)c->lcs_buf;
     a.dst = (int32_t *)(base + p.dst);
     a.dseq = c->shard ? (uint32_t *)(base + p.dseq) : nullptr;
@@ -1721,9 +1733,7 @@ int fb_log_compact(fb_ctx *c, int64_t expect_kept, int64_t *kept_seq, int64_t ca
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     uint32_t live = 0;
-    HIPCHK(c, hipMemcpy(&live, a.loc.tpre + p.ntl, 4, hipMemcpyDeviceToHost));
-    if ((int64_t)live > c->head)
-        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (log head)", live, (long long)c->head);
+    if (int rc_ = read_count(c, a.loc.tpre + p.ntl, "live entries", c->head, "log head", &live)) return rc_;
     if (expect_kept >= 0 && expect_kept != (int64_t)live)
         return fail(c, FB_ESTATE, "the log holds %u live entries, the caller expected %lld", live, (long long)expect_kept);
     if (kept_seq && cap < (int64_t)live)
@@ -1770,8 +1780,7 @@ int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int
             return fail(c, FB_EINVAL, "exchange bitmap: %lld bytes at %p, the log needs %lld, 8-byte aligned", (long long)bytes,
                         device_buffer, (long long)need);
     }
-    const Gate g = life_gate_log_compact_shard_mark(c->life, c->caps);
-    if (int rc_ = enter(c, g)) return rc_;  // (an uncommitted tick's clears are taken back here)
+    if (int rc_ = enter(c, Call::log_compact_shard_mark)) return rc_;  // (an uncommitted tick's clears are taken back here)
     HIPCHK(c, hipSetDevice(c->device));
     const LcPlan p = lcs_plan(c->head, c->head_local, c->W, false);
     if (int rc_ = lc_scratch(c, p.bytes, lcs_full_bytes(c), 0)) return rc_;
@@ -1792,10 +1801,7 @@ int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     uint32_t live = 0;
-    HIPCHK(c, hipMemcpy(&live, a.loc.tpre + p.ntl, 4, hipMemcpyDeviceToHost));
-    if ((int64_t)live > c->head_local)
-        return fail(c, FB_EHIP, "device-reported live entries %u outside [0, %lld] (the log shard's entries)", live,
-                    (long long)c->head_local);
+    if (int rc_ = read_count(c, a.loc.tpre + p.ntl, "live entries", c->head_local, "the log shard's entries", &live)) return rc_;
     c->lcs_head = c->head;
     c->lcs_head_local = c->head_local;
     c->lcs_live = (int64_t)live;
@@ -1807,7 +1813,7 @@ int fb_log_compact_shard_mark(fb_ctx *c, void *device_buffer, int64_t bytes, int
 int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_seq, int64_t cap, int64_t *n_kept_local) {
     if (!c) return FB_EINVAL;
     if (kept_seq && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
-    if (int rc_ = enter(c, life_gate_log_compact_shard_apply(c->life, c->caps))) return rc_;
+    if (int rc_ = enter(c, Call::log_compact_shard_apply)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->head != c->lcs_head || c->head_local != c->lcs_head_local) {  // (the gates keep the log as the mark saw it)
         life_lcs_unmarked(c->life);
@@ -1827,8 +1833,8 @@ int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_s
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
-    uint32_t total = 0;
-    HIPCHK(c, hipMemcpy(&total, a.glob.tpre + p.ntg, 4, hipMemcpyDeviceToHost));
+    uint32_t total = 0;  // (no bound here: the comparison below refuses a wrong count its own way, and unmarks)
+    if (int rc_ = read_count(c, a.glob.tpre + p.ntg, "live entries", UINT32_MAX, "a 32-bit count", &total)) return rc_;
     if ((int64_t)total != n_live_global || n_live_global > c->head || n_live_global < c->lcs_live) {
         life_lcs_unmarked(c->life);
         return fail(c, FB_ESTATE, "the reduced bitmap holds %u live entries, the group agreed on %lld (this rank: %lld of %lld)",
@@ -1864,6 +1870,7 @@ int fb_log_compact_shard_apply(fb_ctx *c, int64_t n_live_global, int64_t *kept_s
 
 int fb_log_compact_shard_cancel(fb_ctx *c) {
     if (!c) return FB_EINVAL;
+    if (int rc_ = enter(c, Call::log_compact_shard_cancel)) return rc_;  // (open in every state, no duties)
     c->lcs_buf = nullptr;
     life_lcs_unmarked(c->life);
     return FB_OK;
@@ -1873,39 +1880,53 @@ int fb_log_compact_shard_cancel(fb_ctx *c) {
 // first (k_lr_flag, k_lc_scan write only the scratch), synchronise, check the caller's room,
 // and only then take.  Nothing of the Life changes: the ticks after it make the launches they
 // would have made without it.
-int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out, int32_t *slot_out, int64_t cap,
-                   int64_t *n_reclaimed) {
+// shard: a rank's part of its group's reclaim (§5g, "A shard group's reclaim").  Whether a local
+// entry goes depends on its own sequence against the bound and on its slot's record, epoch and
+// mask byte, all of which this rank holds -- so there is no exchange, and the call is the same
+// over the shard.  The group agrees (every rank counts, cap = 0) before any rank takes.
+static int log_reclaim_run(fb_ctx *c, bool shard, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out,
+                           int32_t *slot_out, int64_t cap, int64_t *n_reclaimed) {
     if (!c) return FB_EINVAL;
     if (below_seq < 0) return fail(c, FB_EINVAL, "below_seq %lld < 0", (long long)below_seq);
     if ((seq_out || slot_out) && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
-    if (int rc_ = enter(c, life_gate_log_reclaim(c->life, c->caps))) return rc_;
+    // (a dropped launch's in-place clears are taken back here: what its results named is live)
+    if (int rc_ = enter(c, shard ? Call::log_reclaim_shard : Call::log_reclaim)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
-    const LrPlan p = lr_plan(c->head, below_seq, c->W);
-    if (p.nt == 0 || c->W == 0) {  // (an empty prefix, or no slot to hold a record: nothing is launched)
+    const LrPlan p = shard ? lrs_plan(c->head_local, c->W) : lr_plan(c->head, below_seq, c->W);
+    if (p.nt == 0 || c->W == 0) {  // (nothing to walk, or no slot to hold a record: nothing is launched)
         if (n_reclaimed) *n_reclaimed = 0;
         return FB_OK;
     }
-    const size_t full = std::max(lc_plan(c->log_cap, c->W_cap, true).bytes, lr_plan(c->log_cap, c->log_cap, c->W_cap).bytes);
+    const size_t full = shard ? lcs_full_bytes(c)
+                              : std::max(lc_plan(c->log_cap, c->W_cap, true).bytes,
+                                         lr_plan(c->log_cap, c->log_cap, c->W_cap).bytes);
     if (int rc_ = lc_scratch(c, p.bytes, full, 0)) return rc_;
     char *const base = (char *)c->lc_mem;
-    // (the scratch is idle: every call that uses it waits for its launches before it returns)
-    if (slot_mask && c->W) HIPCHK(c, hipMemcpy(base + p.mask, slot_mask, (size_t)c->W, hipMemcpyHostToDevice));
+    // (the scratch is idle: every call that uses it waits for its launches before it returns,
+    // and no mark stands)
+    if (slot_mask) HIPCHK(c, hipMemcpy(base + p.mask, slot_mask, (size_t)c->W, hipMemcpyHostToDevice));
     LrArgs a{};
     a.log = c->log_slot;
-    a.B = p.B;
+    a.B = shard ? std::min(below_seq, c->head) : p.B;  // (a shard's bounds sequences, not entries)
     a.W = c->W;
+    // (no sharded context commits lazily today: the test is kept for the day one does)
     a.live_chk = c->life.stale ? 1 : 0;
     a.reg = c->reg;
     a.epoch = c->epoch;
     a.mask = slot_mask ? (const uint8_t *)(base + p.mask) : nullptr;
-    a.t = LcTable{(unsigned long long *)(base + p.tab.bits), (uint32_t *)(base + p.tab.wrel), (uint32_t *)(base + p.tab.tcnt),
-                  (uint32_t *)(base + p.tab.tpre), p.nt};
+    a.t = lc_table(base, p.tab, p.nt);
     a.seq_out = seq_out ? (int64_t *)(base + p.seq) : nullptr;
     a.slot_out = slot_out ? (int32_t *)(base + p.slot) : nullptr;
-    a.bud = c->caps.clears == Clears::deferred ? c->bud : nullptr;
+    // (sharded contexts keep no per-slot budget)
+    a.bud = !shard && c->caps.clears == Clears::deferred ? c->bud : nullptr;
+    if (shard) {
+        a.seq = c->lseq;
+        a.n = c->head_local;
+        a.slot_base = c->slot_base;
+    }
     {
         Timer t(c, "lr_flag");
-        launch_lr_flag(a, false, t.st());
+        launch_lr_flag(a, shard, t.st());
     }
     {
         Timer t(c, "lc_scan");
@@ -1914,16 +1935,16 @@ int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
     uint32_t n = 0;
-    HIPCHK(c, hipMemcpy(&n, a.t.tpre + p.nt, 4, hipMemcpyDeviceToHost));
-    if ((int64_t)n > p.B)
-        return fail(c, FB_EHIP, "device-reported reclaimed entries %u outside [0, %lld] (the prefix)", n, (long long)p.B);
+    if (int rc_ = read_count(c, a.t.tpre + p.nt, "reclaimed entries", shard ? c->head_local : p.B,
+                             shard ? "the log shard's entries" : "the prefix", &n))
+        return rc_;
     if (n_reclaimed) *n_reclaimed = (int64_t)n;
     if ((seq_out || slot_out) && cap < (int64_t)n)
         return fail(c, FB_EINVAL, "the outputs hold %lld entries, the call reclaims %u", (long long)cap, n);
     if (!n) return FB_OK;
     {
         Timer t(c, "lr_take");
-        launch_lr_take(a, false, t.st());
+        launch_lr_take(a, shard, t.st());
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, stream_wait(c));
@@ -1931,75 +1952,13 @@ int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64
     if (slot_out) HIPCHK(c, hipMemcpy(slot_out, a.slot_out, (size_t)n * 4, hipMemcpyDeviceToHost));
     return FB_OK;
 }
-
-// A rank's part of its group's reclaim ("A shard group's reclaim"): whether a
-// local entry goes depends on its own sequence against the bound and on its slot's record, epoch
-// and mask byte, all of which this rank holds -- so there is no exchange, and the call is
-// fb_log_reclaim's over the shard: count first, check the caller's room, only then take.  The
-// group agrees (every rank counts, cap = 0) before any rank takes.
+int fb_log_reclaim(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out, int32_t *slot_out, int64_t cap,
+                   int64_t *n_reclaimed) {
+    return log_reclaim_run(c, false, below_seq, slot_mask, seq_out, slot_out, cap, n_reclaimed);
+}
 int fb_log_reclaim_shard(fb_ctx *c, int64_t below_seq, const uint8_t *slot_mask, int64_t *seq_out, int32_t *slot_out,
                          int64_t cap, int64_t *n_reclaimed) {
-    if (!c) return FB_EINVAL;
-    if (below_seq < 0) return fail(c, FB_EINVAL, "below_seq %lld < 0", (long long)below_seq);
-    if ((seq_out || slot_out) && cap < 0) return fail(c, FB_EINVAL, "cap %lld < 0", (long long)cap);
-    // (a dropped launch's in-place clears are taken back here: what its results named is live)
-    if (int rc_ = enter(c, life_gate_log_reclaim_shard(c->life, c->caps))) return rc_;
-    HIPCHK(c, hipSetDevice(c->device));
-    const LrPlan p = lrs_plan(c->head_local, c->W);
-    if (p.nt == 0 || c->W == 0) {  // (an empty shard, or a rank that owns no slot: nothing is launched)
-        if (n_reclaimed) *n_reclaimed = 0;
-        return FB_OK;
-    }
-    if (int rc_ = lc_scratch(c, p.bytes, lcs_full_bytes(c), 0)) return rc_;
-    char *const base = (char *)c->lc_mem;
-    // (the scratch is idle: every call that uses it waits for its launches before it returns,
-    // and no mark stands)
-    if (slot_mask) HIPCHK(c, hipMemcpy(base + p.mask, slot_mask, (size_t)c->W, hipMemcpyHostToDevice));
-    LrArgs a{};
-    a.log = c->log_slot;
-    a.B = std::min(below_seq, c->head);
-    a.W = c->W;
-    // (no sharded context commits lazily today: the test is kept for the day one does)
-    a.live_chk = c->life.stale ? 1 : 0;
-    a.reg = c->reg;
-    a.epoch = c->epoch;
-    a.mask = slot_mask ? (const uint8_t *)(base + p.mask) : nullptr;
-    a.t = LcTable{(unsigned long long *)(base + p.tab.bits), (uint32_t *)(base + p.tab.wrel), (uint32_t *)(base + p.tab.tcnt),
-                  (uint32_t *)(base + p.tab.tpre), p.nt};
-    a.seq_out = seq_out ? (int64_t *)(base + p.seq) : nullptr;
-    a.slot_out = slot_out ? (int32_t *)(base + p.slot) : nullptr;
-    a.bud = nullptr;  // (sharded contexts keep no per-slot budget)
-    a.seq = c->lseq;
-    a.n = c->head_local;
-    a.slot_base = c->slot_base;
-    {
-        Timer t(c, "lr_flag");
-        launch_lr_flag(a, true, t.st());
-    }
-    {
-        Timer t(c, "lc_scan");
-        launch_lc_scan(a.t, t.st());
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, stream_wait(c));
-    uint32_t n = 0;
-    HIPCHK(c, hipMemcpy(&n, a.t.tpre + p.nt, 4, hipMemcpyDeviceToHost));
-    if ((int64_t)n > c->head_local)
-        return fail(c, FB_EHIP, "device-reported reclaimed entries %u outside [0, %lld] (the log shard's entries)", n,
-                    (long long)c->head_local);
-    if (n_reclaimed) *n_reclaimed = (int64_t)n;
-    if ((seq_out || slot_out) && cap < (int64_t)n)
-        return fail(c, FB_EINVAL, "the outputs hold %lld entries, the call reclaims %u", (long long)cap, n);
-    if (!n) return FB_OK;
-    {
-        Timer t(c, "lr_take");
-        launch_lr_take(a, true, t.st());
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, stream_wait(c));
-    if (seq_out) HIPCHK(c, hipMemcpy(seq_out, a.seq_out, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (slot_out) HIPCHK(c, hipMemcpy(slot_out, a.slot_out, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return FB_OK;
+    return log_reclaim_run(c, true, below_seq, slot_mask, seq_out, slot_out, cap, n_reclaimed);
 }
 
 // The committed pool summarised on the device.  The three launches write only
@@ -2025,7 +1984,7 @@ static int pool_stats_run(fb_ctx *c, bool shard, double now, double tte, const d
             return fail(c, FB_EINVAL, "now %g / tte %g must be finite", now, tte);
     }
     // (its flush: observably an immediate commit)
-    if (int rc_ = shard ? enter(c, life_gate_pool_stats_shard(c->life, c->caps)) : enter(c, Call::pool_stats)) return rc_;
+    if (int rc_ = enter(c, shard ? Call::pool_stats_shard : Call::pool_stats)) return rc_;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->ps_out) {
         if (hipHostMalloc((void **)&c->ps_out, kPsCols * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
@@ -2037,19 +1996,10 @@ static int pool_stats_run(fb_ctx *c, bool shard, double now, double tte, const d
     }
     const int64_t head = shard ? c->head_local : c->head;  // the entries this context's log holds
     const PsPlan p = ps_plan(c->W, c->Qn, head);
-    if (p.bytes > c->ps_cap) {
-        // sized for this state, doubling, never beyond a full table, queue and log
-        const size_t full = ps_plan(c->W_cap, std::max<int64_t>(c->qcap, c->Wq_cap), c->log_cap).bytes;
-        const size_t want = std::max(p.bytes, std::min(2 * c->ps_cap, full));
-        HIPCHK(c, stream_wait(c));
-        void *m = nullptr;
-        const hipError_t e = hipMalloc(&m, want);
-        if (e != hipSuccess)
-            return fail(c, FB_ENOMEM, "hipMalloc(pool summary scratch %zu B) failed: %s", want, hipGetErrorString(e));
-        if (c->ps_mem) hipFree(c->ps_mem);
-        c->ps_mem = m;
-        c->ps_cap = want;
-    }
+    // (never beyond a full table, queue and log)
+    if (int rc_ = scratch_grow(c, "pool summary scratch", c->ps_mem, c->ps_cap, p.bytes,
+                               ps_plan(c->W_cap, std::max<int64_t>(c->qcap, c->Wq_cap), c->log_cap).bytes, 0))
+        return rc_;
     char *const base = (char *)c->ps_mem;
     PsArgs a{};
     a.now = hbc ? now : 0.0;

@@ -58,9 +58,11 @@ inline int life_phase(const Life &l) { return l.pos == Pos::phase1 ? 1 : life_la
 // fb_purge_launch, fb_purge, fb_assign and fb_apply_events are sequences of these.)
 #define FB_LIFE_CALLS(X)                                                                          \
     X(load_state) X(load_shard) X(read_state) X(read_inflight) X(read_shard_log) X(device_view)   \
-    X(log_compact) X(pool_stats) X(exchange_bytes) X(stage) X(launch) X(tick_continue) X(wait)    \
-    X(commit) X(get_local_assignments) X(get_assignments) X(get_orphans) X(get_evicted)           \
-    X(get_outputs) X(get_outputs_compact) X(expand_compact) X(get_event_status) X(set_window)     \
+    X(log_compact) X(pool_stats) X(pool_stats_shard) X(log_reclaim) X(log_reclaim_shard)          \
+    X(log_compact_shard_mark) X(log_compact_shard_apply) X(log_compact_shard_cancel)              \
+    X(exchange_bytes) X(stage) X(launch) X(tick_continue) X(wait) X(commit)                       \
+    X(get_local_assignments) X(get_assignments) X(get_orphans) X(get_evicted) X(get_outputs)      \
+    X(get_outputs_compact) X(expand_compact) X(get_event_status) X(set_window)                    \
     X(set_eager_commit) X(set_compact_out) X(set_full_assign) X(set_round_hint) X(set_path)       \
     X(debug_read) X(sync)
 enum class Call : uint8_t {
@@ -80,7 +82,7 @@ enum Duty : unsigned {
     kFlush = 1,     // the deferred commit as its own launch (also before a refusal that names it)
     kUndo = 2,      // take back the in-place clears of a launch that never commits
     kUndoSync = 4,  // ... and wait for the stream: the log leaves the context's stream
-    kDiscard = 8,   // the call, once it succeeds, discards the FB_ENOSPC tick (life_replaced)
+    kDiscard = 8,   // the call, once it succeeds, discards the uncommitted tick (life_replaced, life_lcs_marked)
 };
 // refuse: the FB_ESTATE message, or null: go on.  A refusal carries at most kFlush.
 struct Gate {
@@ -89,6 +91,12 @@ struct Gate {
 };
 
 constexpr const char *kLifeMarkedRefusal = "a log compaction is marked: apply or cancel first";
+
+// The three refusals of a call that runs between ticks only, under the call's name.
+#define FB_BETWEEN_TICKS(name)                                                                    \
+    between_ticks(name " with staged events pending: launch and commit their tick first",         \
+                  name " between a tick's wait and its commit: fb_tick_commit first",             \
+                  name " with a tick launched: fb_tick_wait and fb_tick_commit first")
 
 inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     const bool launched = life_launched(l), waited = life_waited(l), in_flight = launched && !waited;
@@ -100,11 +108,25 @@ inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     const unsigned undo = (l.undo_E > 0 && (l.pos == Pos::failed || l.pos == Pos::dropped)) ? kUndo : 0;
     const auto no = [](const char *m, unsigned d = 0) { return Gate{m, d}; };
     const auto ok = [](unsigned d = 0) { return Gate{nullptr, d}; };
-    // between a group compaction's mark and its apply the ranks hold a bitmap of this log: every
-    // call that reads or changes the log or launches a tick waits (fb_pool_stats_shard, whose
-    // gate ends here, too); what touches neither goes on
-    if (l.marked && call != Call::exchange_bytes && call != Call::debug_read && call != Call::sync)
-        return no(kLifeMarkedRefusal);
+    // Between ticks only -- nothing staged, nothing launched -- and then the flush and the undo:
+    // the calls that read or edit the committed pool and log on the device.  The undo comes
+    // first: a launch the wait dropped has its in-place clears taken back, so the entries its
+    // results named count as live.
+    const auto between_ticks = [&](const char *m_staged, const char *m_waited, const char *m_launched) {
+        if (l.staged) return no(m_staged);
+        if (waited) return no(m_waited);
+        if (launched) return no(m_launched);
+        return ok(flush | undo);
+    };
+    // Between a group compaction's mark and its apply the ranks hold a bitmap of this log: every
+    // call that reads or changes the log or launches a tick waits.  What touches neither goes
+    // on, and so do the two calls that end the mark.
+    const bool held = l.marked && call != Call::exchange_bytes && call != Call::debug_read && call != Call::sync &&
+                      call != Call::log_compact_shard_apply && call != Call::log_compact_shard_cancel;
+    // (four calls name a wrong context kind before they say "marked": points no context reaches)
+    const bool kind_first = call == Call::pool_stats_shard || call == Call::log_reclaim ||
+                            call == Call::log_reclaim_shard || call == Call::log_compact_shard_mark;
+    if (held && !kind_first) return no(kLifeMarkedRefusal);
     switch (call) {
     case Call::load_state:  // (accepted over any tick, window ticks included; a staged batch stays)
         return k.sharded ? no("sharded context: use fb_load_shard", flush) : ok(flush);
@@ -133,10 +155,41 @@ inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
         return ok(flush | undo | (launched ? kDiscard : 0));
     case Call::pool_stats:
         if (k.sharded) return no("fb_pool_stats on a sharded context: the pool is the group's, a summary needs a collective");
-        if (l.staged) return no("fb_pool_stats with staged events pending: launch and commit their tick first");
-        if (waited) return no("fb_pool_stats between a tick's wait and its commit: fb_tick_commit first");
-        if (launched) return no("fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first");
-        return ok(flush | undo);
+        return FB_BETWEEN_TICKS("fb_pool_stats");
+    case Call::pool_stats_shard:  // a rank's part of its group's summary
+        if (!k.sharded) return no("fb_pool_stats_shard on a one-GPU context: use fb_pool_stats", flush);
+        if (held) return no(kLifeMarkedRefusal);
+        return FB_BETWEEN_TICKS("fb_pool_stats");  // (a wart callers see: fb_pool_stats' name, not this call's)
+    case Call::log_reclaim:
+        // A deque context has no liveness, so nothing to reclaim from.  A sharded context's
+        // sequences are global across the ranks and its bound is the group's: the rank's part is
+        // fb_log_reclaim_shard.  (Neither refusal carries a duty, not even the flush.)
+        if (k.deque) return no("fb_log_reclaim on a deque context: it keeps no liveness, nothing is in flight on a record");
+        if (k.sharded)
+            return no("fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (unlike "
+                      "fb_log_compact_shard_mark / _apply it needs no exchange): use fb_log_reclaim_shard");
+        if (held) return no(kLifeMarkedRefusal);
+        return FB_BETWEEN_TICKS("fb_log_reclaim");
+    case Call::log_reclaim_shard:  // a rank's part of its group's reclaim: no exchange, it renumbers nothing
+        if (!k.sharded) return no("fb_log_reclaim_shard on a one-GPU context: use fb_log_reclaim", flush);
+        if (held) return no(kLifeMarkedRefusal);
+        return FB_BETWEEN_TICKS("fb_log_reclaim_shard");
+    case Call::log_compact_shard_mark:
+        // A rank's first half of its group's compaction.  Like a load it discards a tick that was
+        // never committed -- waited for (another rank failed), failed or dropped -- after taking
+        // its in-place clears back (kDiscard: life_lcs_marked).  A tick in flight may still write
+        // the log, staged events carry sequences of the old numbering, and an eager commit (no
+        // sharded context enqueues one) would have moved the committed state already.
+        if (!k.sharded) return no("fb_log_compact_shard_mark on a one-GPU context: use fb_log_compact", flush);
+        if (held) return no(kLifeMarkedRefusal);  // (a second mark: no duties)
+        if (l.staged) return no("fb_log_compact_shard_mark with staged events pending: their sequences would go stale");
+        if (l.pos == Pos::phase1 || l.pos == Pos::launched || (launched && l.eager))
+            return no("fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first");
+        return ok(flush | (l.undo_E > 0 ? kUndo : 0) | (launched ? kDiscard : 0));
+    case Call::log_compact_shard_apply:  // only after a mark (which left no tick, nothing staged, nothing owed)
+        if (!k.sharded) return no("fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact", flush);
+        return !l.marked ? no("fb_log_compact_shard_apply without fb_log_compact_shard_mark") : ok();  // (no duties)
+    case Call::log_compact_shard_cancel:  // (drops a mark if there is one: in every state, on every kind)
     case Call::exchange_bytes:
     case Call::stage:
         return ok();
@@ -187,86 +240,7 @@ inline Gate life_gate(const Life &l, const CtxCaps &k, Call call) {
     }
     return no("unknown call");
 }
-
-// fb_pool_stats_shard, a rank's part of its group's summary: fb_pool_stats' gate on the rank
-// with the sharded refusal lifted -- the same refusals at every point of a tick, the same
-// flush and undo -- and a refusal of its own where fb_pool_stats answers.  (No Call of its
-// own: it is that call's place in a tick's life.)
-inline Gate life_gate_pool_stats_shard(const Life &l, const CtxCaps &k) {
-    if (!k.sharded)
-        return Gate{"fb_pool_stats_shard on a one-GPU context: use fb_pool_stats", l.cm_pending ? (unsigned)kFlush : 0u};
-    CtxCaps one = k;
-    one.sharded = false;
-    return life_gate(l, one, Call::pool_stats);
-}
-
-// fb_log_reclaim, live entries of workers that stay registered completed between ticks:
-// fb_pool_stats' gate -- the same refusals at every point of a tick, the same flush and undo --
-// with two refusals of its own.  A deque context has no liveness, so nothing to reclaim from.  A
-// sharded context's sequences are global across the ranks and its bound is the group's: the
-// rank's part is fb_log_reclaim_shard (below), which needs no mark / all-reduce / apply the way
-// fb_log_compact_shard_mark / _apply do, since it renumbers nothing.  It makes
-// no transition: the Life after a success is the Life before it (a window stays a window, a
-// stale log stale).  (No Call of its own, as fb_pool_stats_shard.)
-inline Gate life_gate_log_reclaim(const Life &l, const CtxCaps &k) {
-    if (k.deque) return Gate{"fb_log_reclaim on a deque context: it keeps no liveness, nothing is in flight on a record", 0u};
-    if (k.sharded)
-        return Gate{"fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (unlike "
-                    "fb_log_compact_shard_mark / _apply it needs no exchange): use fb_log_reclaim_shard",
-                    0u};
-    Gate g = life_gate(l, k, Call::pool_stats);
-    if (g.refuse) {
-        // (fb_pool_stats' refusals at a point of a tick, under this call's name)
-        if (l.marked) return g;
-        if (l.staged) return Gate{"fb_log_reclaim with staged events pending: launch and commit their tick first", g.duties};
-        if (life_waited(l)) return Gate{"fb_log_reclaim between a tick's wait and its commit: fb_tick_commit first", g.duties};
-        return Gate{"fb_log_reclaim with a tick launched: fb_tick_wait and fb_tick_commit first", g.duties};
-    }
-    return g;
-}
-
-// fb_log_reclaim_shard, a rank's part of its group's reclaim: built from fb_pool_stats' gate the
-// way fb_pool_stats_shard's is -- the sharded refusal lifted, the same refusals at every point
-// of a tick (under this call's name), the same flush and undo -- and a refusal of its own where
-// fb_log_reclaim answers.  The undo comes first: a launch the wait dropped has its in-place
-// clears taken back, so the entries its results named count as live.  No transition.
-inline Gate life_gate_log_reclaim_shard(const Life &l, const CtxCaps &k) {
-    if (!k.sharded)
-        return Gate{"fb_log_reclaim_shard on a one-GPU context: use fb_log_reclaim", l.cm_pending ? (unsigned)kFlush : 0u};
-    const Gate g = life_gate_pool_stats_shard(l, k);
-    if (g.refuse) {
-        if (l.marked) return g;  // (kLifeMarkedRefusal)
-        if (l.staged) return Gate{"fb_log_reclaim_shard with staged events pending: launch and commit their tick first", g.duties};
-        if (life_waited(l)) return Gate{"fb_log_reclaim_shard between a tick's wait and its commit: fb_tick_commit first", g.duties};
-        return Gate{"fb_log_reclaim_shard with a tick launched: fb_tick_wait and fb_tick_commit first", g.duties};
-    }
-    return g;
-}
-
-// fb_log_compact_shard_mark, a rank's first half of its group's compaction.  Like a load it
-// discards a tick that was never committed -- waited for (another rank failed), failed or
-// dropped -- after taking its in-place clears back (kUndo; kDiscard: life_lcs_marked).  A tick
-// in flight may still write the log, staged events carry sequences of the old numbering, and an
-// eager commit (no sharded context enqueues one) would have moved the committed state already.
-inline Gate life_gate_log_compact_shard_mark(const Life &l, const CtxCaps &k) {
-    const unsigned flush = l.cm_pending ? (unsigned)kFlush : 0u;
-    if (!k.sharded) return Gate{"fb_log_compact_shard_mark on a one-GPU context: use fb_log_compact", flush};
-    if (l.marked) return Gate{kLifeMarkedRefusal, 0u};
-    if (l.staged)
-        return Gate{"fb_log_compact_shard_mark with staged events pending: their sequences would go stale", 0u};
-    if (l.pos == Pos::phase1 || l.pos == Pos::launched || (life_launched(l) && l.eager))
-        return Gate{"fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first", 0u};
-    const unsigned undo = l.undo_E > 0 ? (unsigned)kUndo : 0u, discard = life_launched(l) ? (unsigned)kDiscard : 0u;
-    return Gate{nullptr, flush | undo | discard};
-}
-// fb_log_compact_shard_apply: only after a mark (which left no tick, nothing staged, nothing owed)
-inline Gate life_gate_log_compact_shard_apply(const Life &l, const CtxCaps &k) {
-    if (!k.sharded)
-        return Gate{"fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact",
-                    l.cm_pending ? (unsigned)kFlush : 0u};
-    if (!l.marked) return Gate{"fb_log_compact_shard_apply without fb_log_compact_shard_mark", 0u};
-    return Gate{};
-}
+#undef FB_BETWEEN_TICKS
 
 // The second gate, where a log pointer or copy is handed out: the deferred clears of the
 // entries lazy commits left, all at once (after the flush above).

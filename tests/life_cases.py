@@ -12,6 +12,12 @@ uncommitted launch's), "sync" (and waited for the stream), "discard" (fb_log_com
 FB_ENOSPC tick).  actions() lists what can happen next, apply() the Raw afterwards, steps()
 the life_* transitions faasbal_api.hip runs for the same action.
 
+The maintenance calls that came after that library (fb_pool_stats_shard, fb_log_reclaim,
+fb_log_reclaim_shard, fb_log_compact_shard_mark / _apply / _cancel) and the `marked` flag the
+mark sets are in the same table: gate() states their rules as their pull requests did, and on
+the sharded kind actions() adds a successful mark, apply and cancel, so the closure reaches
+the marked state.  On the other kinds `marked` stays 0 in every reachable state.
+
 The one deliberate difference (LOAD_REJECTED_KEEPS_STALE): the old fb_load_state /
 fb_load_shard cleared stale_any before validating, so a rejected load switched the liveness
 test off over a log that still held stale entries.
@@ -24,21 +30,25 @@ DEFERRED = ("hb",)                  # bud / ev_clr; every other kind notes in-pl
 LOAD_REJECTED_KEEPS_STALE = True
 
 CALLS = ("load_state", "load_shard", "read_state", "read_inflight", "read_shard_log", "device_view", "log_compact",
-         "pool_stats", "exchange_bytes", "stage", "launch", "tick_continue", "wait", "commit", "get_local_assignments",
-         "get_assignments", "get_orphans", "get_evicted", "get_outputs", "get_outputs_compact", "expand_compact",
-         "get_event_status", "set_window", "set_eager_commit", "set_compact_out", "set_full_assign", "set_round_hint",
-         "set_path", "debug_read", "sync")
+         "pool_stats", "pool_stats_shard", "log_reclaim", "log_reclaim_shard", "log_compact_shard_mark",
+         "log_compact_shard_apply", "log_compact_shard_cancel", "exchange_bytes", "stage", "launch", "tick_continue", "wait",
+         "commit", "get_local_assignments", "get_assignments", "get_orphans", "get_evicted", "get_outputs",
+         "get_outputs_compact", "expand_compact", "get_event_status", "set_window", "set_eager_commit", "set_compact_out",
+         "set_full_assign", "set_round_hint", "set_path", "debug_read", "sync")
 WAITS = ("ok", "rerun", "rerun_general", "invalid_message", "lengths_rejected", "log_full", "too_narrow",
          "relaunch_wanted", "other")
 
+# marked: fb_log_compact_shard_mark done, its apply or cancel to come (the one flag the old context
+# did not have: the maintenance calls came after it, and their rules are written below as the
+# pull requests that added them stated them)
 Raw = collections.namedtuple("Raw", "staged launched waited l_failed l_enospc l_eager phase undo_E cm_pending "
-                                    "stale_any l_win")
-CREATED = Raw(False, False, False, False, False, False, 0, 0, False, False, False)
+                                    "stale_any l_win marked")
+CREATED = Raw(False, False, False, False, False, False, 0, 0, False, False, False, False)
 E_MSGS = 3  # messages of a launch that carries some
 
 
 def canon(kind, r):
-    """The Life of a Raw: "staged,pos,win,eager,enospc,cm_pending,undo_E,stale" (tests/life_probe.cpp)."""
+    """The Life of a Raw: "staged,pos,win,eager,enospc,cm_pending,undo_E,stale,marked" (tests/life_probe.cpp)."""
     if r.launched and r.waited:
         pos = "waited"
     elif r.launched and r.l_failed:
@@ -52,12 +62,40 @@ def canon(kind, r):
     else:
         pos = "none"
     live = pos not in ("none", "dropped")
-    return "%d,%s,%d,%d,%d,%d,%d,%d" % (r.staged, pos, live and r.l_win, live and r.l_eager,
-                                        pos == "failed" and r.l_enospc, r.cm_pending, r.undo_E, r.stale_any)
+    return "%d,%s,%d,%d,%d,%d,%d,%d,%d" % (r.staged, pos, live and r.l_win, live and r.l_eager,
+                                           pos == "failed" and r.l_enospc, r.cm_pending, r.undo_E, r.stale_any, r.marked)
 
 
 WIN_MSG = "%s between the launch and the commit of a window tick: fb_tick_commit first"
 NO_WAITED = "no waited tick"
+MARKED = "a log compaction is marked: apply or cancel first"
+# what touches neither the log nor a tick goes on while a compaction is marked, and so do the two
+# calls that end the mark
+MARKED_PASSES = ("exchange_bytes", "debug_read", "sync", "log_compact_shard_apply", "log_compact_shard_cancel")
+# ... and four calls name a wrong context kind before they say "marked" (points no context reaches)
+KIND_FIRST = ("pool_stats_shard", "log_reclaim", "log_reclaim_shard", "log_compact_shard_mark")
+ONE_GPU = {"pool_stats_shard": "fb_pool_stats_shard on a one-GPU context: use fb_pool_stats",
+           "log_reclaim_shard": "fb_log_reclaim_shard on a one-GPU context: use fb_log_reclaim",
+           "log_compact_shard_mark": "fb_log_compact_shard_mark on a one-GPU context: use fb_log_compact",
+           "log_compact_shard_apply": "fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact"}
+RECLAIM_DEQUE = "fb_log_reclaim on a deque context: it keeps no liveness, nothing is in flight on a record"
+RECLAIM_SHARDED = ("fb_log_reclaim on a sharded context: its sequence numbers are global across ranks (unlike "
+                   "fb_log_compact_shard_mark / _apply it needs no exchange): use fb_log_reclaim_shard")
+MARK_STAGED = "fb_log_compact_shard_mark with staged events pending: their sequences would go stale"
+MARK_IN_FLIGHT = "fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first"
+APPLY_UNMARKED = "fb_log_compact_shard_apply without fb_log_compact_shard_mark"
+
+
+def between_ticks(name, r, duties):
+    """Between ticks only: refused with staged events, between wait and commit, with a tick
+    launched, under the name given; otherwise `duties` (the flush, the undo of a failed launch)."""
+    if r.staged:
+        return name + " with staged events pending: launch and commit their tick first", []
+    if r.launched and r.waited:
+        return name + " between a tick's wait and its commit: fb_tick_commit first", []
+    if r.launched:
+        return name + " with a tick launched: fb_tick_wait and fb_tick_commit first", []
+    return None, duties
 
 
 def gate(kind, r, call):
@@ -66,6 +104,8 @@ def gate(kind, r, call):
     flush = ["flush"] if r.cm_pending else []
     undo_failed = ["undo"] if r.undo_E > 0 and r.l_failed else []
     win_uncommitted = r.launched and r.l_win
+    if r.marked and call not in MARKED_PASSES + KIND_FIRST:
+        return MARKED, []
     if call == "load_state":
         return ("sharded context: use fb_load_shard" if shard else None), flush
     if call == "load_shard":
@@ -99,13 +139,33 @@ def gate(kind, r, call):
     if call == "pool_stats":
         if shard:
             return "fb_pool_stats on a sharded context: the pool is the group's, a summary needs a collective", []
+        return between_ticks("fb_pool_stats", r, flush + undo_failed)
+    if call in ONE_GPU and not shard:  # (whatever the state; at most the flush)
+        return ONE_GPU[call], flush
+    if call == "log_reclaim" and (deque or shard):  # (no duties, not even the flush)
+        return (RECLAIM_DEQUE if deque else RECLAIM_SHARDED), []
+    if call in KIND_FIRST and r.marked:
+        return MARKED, []
+    if call == "pool_stats_shard":
+        # fb_pool_stats' refusals and duties with the sharded refusal set aside (its name in the texts too)
+        return between_ticks("fb_pool_stats", r, flush + undo_failed)
+    if call == "log_reclaim":
+        return between_ticks("fb_log_reclaim", r, flush + undo_failed)
+    if call == "log_reclaim_shard":
+        # refused exactly where fb_pool_stats_shard is, under its own name; a dropped launch's
+        # clears are taken back first: the entries its results named count as live
+        return between_ticks("fb_log_reclaim_shard", r, flush + undo_failed)
+    if call == "log_compact_shard_mark":
         if r.staged:
-            return "fb_pool_stats with staged events pending: launch and commit their tick first", []
-        if r.launched and r.waited:
-            return "fb_pool_stats between a tick's wait and its commit: fb_tick_commit first", []
-        if r.launched:
-            return "fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first", []
-        return None, flush + undo_failed
+            return MARK_STAGED, []
+        if r.launched and (r.l_eager or not (r.waited or r.l_failed)):  # phase1, launched, or committed eagerly
+            return MARK_IN_FLIGHT, []
+        # a waited-uncommitted, failed or dropped tick is discarded, its clears taken back first
+        return None, flush + (["undo"] if r.undo_E > 0 else []) + (["discard"] if r.launched else [])
+    if call == "log_compact_shard_apply":  # only after a mark
+        return (None if r.marked else APPLY_UNMARKED), []
+    if call == "log_compact_shard_cancel":  # in every state, on every kind: it drops a mark if there is one
+        return None, []
     if call in ("exchange_bytes", "stage"):
         return None, []
     if call == "launch":
@@ -163,13 +223,15 @@ def gate(kind, r, call):
 # what a call that passed its gate goes on to do to the flags, by variant:
 #   "ok"        it succeeds;  "rejected"  its arguments (or fb_log_compact's expect_kept) are refused
 #   "log"       fb_read_state asked for the log / fb_device_view_get / fb_set_path("lazy", 0): log_settle
+#   "unmarked"  fb_log_compact_shard_apply's count disagreed with the group's: the mark is dropped
 VARIANTS = {"load_state": ("ok", "rejected"), "load_shard": ("ok", "rejected"), "log_compact": ("ok", "rejected"),
-            "read_state": ("ok", "log"), "device_view": ("log",), "set_path": ("ok", "log")}
+            "read_state": ("ok", "log"), "device_view": ("log",), "set_path": ("ok", "log"),
+            "log_compact_shard_apply": ("ok", "unmarked")}
 
 
 def actions(kind, r):
     """Every next step of a context of this kind in this state: (name, args...)."""
-    out = [("stage", 1), ("stage", 0)]
+    out = [("stage", 1), ("stage", 0)] if gate(kind, r, "stage")[0] is None else []  # (refused while marked)
     if gate(kind, r, "launch")[0] is None:
         out += [("launch", 0, 0, 0), ("launch", E_MSGS, 0, 0)]
         if kind in LISTS:  # plan_window: messages, lists (fb_set_window allocates the buffers on "hb")
@@ -257,6 +319,12 @@ def apply(kind, r, act):
             r = r._replace(stale_any=False)
     elif call == "log_compact" and v == "ok":
         r = r._replace(stale_any=False, launched=False, waited=False, undo_E=0, l_enospc=False)
+    elif call == "log_compact_shard_mark":  # the uncommitted tick is gone, the committed state is what it was
+        r = r._replace(launched=False, waited=False, undo_E=0, marked=True)
+    elif call == "log_compact_shard_apply" and v == "ok":
+        r = r._replace(stale_any=False, launched=False, waited=False, undo_E=0, marked=False)
+    elif call == "log_compact_shard_cancel" or v == "unmarked":
+        r = r._replace(marked=False)
     elif v == "log":
         r = r._replace(stale_any=False)  # log_settle (its flush ran above)
     return None, duties, r
@@ -279,8 +347,12 @@ def steps(act, duties, settle_due):
     _, call, v = act
     if v == "log" and settle_due:
         pre.append("settled")
-    if v == "ok" and call in ("load_state", "load_shard", "log_compact"):
+    if v == "ok" and call in ("load_state", "load_shard", "log_compact", "log_compact_shard_apply"):
         pre.append("replaced")
+    if call == "log_compact_shard_mark":
+        pre.append("marked")
+    if call == "log_compact_shard_cancel" or v == "unmarked":
+        pre.append("unmarked")
     return pre
 
 
@@ -300,54 +372,55 @@ def closure(kind):
 # The Lifes of closure(kind), written out: the table's rows.  (python tests/life_cases.py prints them.)
 STATES = {
     "hb": (
-        "0,failed,0,0,0,0,0,0", "0,failed,0,0,0,0,0,1", "0,failed,0,0,1,0,0,0", "0,failed,0,0,1,0,0,1",
-        "0,failed,1,0,0,0,0,0", "0,failed,1,0,0,0,0,1", "0,failed,1,0,1,0,0,0", "0,failed,1,0,1,0,0,1",
-        "0,failed,1,1,0,0,0,0", "0,failed,1,1,0,0,0,1", "0,launched,0,0,0,0,0,0", "0,launched,0,0,0,0,0,1",
-        "0,launched,1,0,0,0,0,0", "0,launched,1,0,0,0,0,1", "0,launched,1,1,0,0,0,0", "0,launched,1,1,0,0,0,1",
-        "0,none,0,0,0,0,0,0", "0,none,0,0,0,0,0,1", "0,none,0,0,0,1,0,0", "0,none,0,0,0,1,0,1",
-        "0,waited,0,0,0,0,0,0", "0,waited,0,0,0,0,0,1", "0,waited,1,0,0,0,0,0", "0,waited,1,0,0,0,0,1",
-        "0,waited,1,1,0,0,0,0", "0,waited,1,1,0,0,0,1", "1,failed,0,0,0,0,0,0", "1,failed,0,0,0,0,0,1",
-        "1,failed,0,0,1,0,0,0", "1,failed,0,0,1,0,0,1", "1,failed,1,0,0,0,0,0", "1,failed,1,0,0,0,0,1",
-        "1,failed,1,0,1,0,0,0", "1,failed,1,0,1,0,0,1", "1,failed,1,1,0,0,0,0", "1,failed,1,1,0,0,0,1",
-        "1,launched,0,0,0,0,0,0", "1,launched,0,0,0,0,0,1", "1,launched,1,0,0,0,0,0", "1,launched,1,0,0,0,0,1",
-        "1,launched,1,1,0,0,0,0", "1,launched,1,1,0,0,0,1", "1,none,0,0,0,0,0,0", "1,none,0,0,0,0,0,1",
-        "1,none,0,0,0,1,0,0", "1,none,0,0,0,1,0,1", "1,waited,0,0,0,0,0,0", "1,waited,0,0,0,0,0,1",
-        "1,waited,1,0,0,0,0,0", "1,waited,1,0,0,0,0,1", "1,waited,1,1,0,0,0,0", "1,waited,1,1,0,0,0,1",
+        "0,failed,0,0,0,0,0,0,0", "0,failed,0,0,0,0,0,1,0", "0,failed,0,0,1,0,0,0,0", "0,failed,0,0,1,0,0,1,0",
+        "0,failed,1,0,0,0,0,0,0", "0,failed,1,0,0,0,0,1,0", "0,failed,1,0,1,0,0,0,0", "0,failed,1,0,1,0,0,1,0",
+        "0,failed,1,1,0,0,0,0,0", "0,failed,1,1,0,0,0,1,0", "0,launched,0,0,0,0,0,0,0", "0,launched,0,0,0,0,0,1,0",
+        "0,launched,1,0,0,0,0,0,0", "0,launched,1,0,0,0,0,1,0", "0,launched,1,1,0,0,0,0,0", "0,launched,1,1,0,0,0,1,0",
+        "0,none,0,0,0,0,0,0,0", "0,none,0,0,0,0,0,1,0", "0,none,0,0,0,1,0,0,0", "0,none,0,0,0,1,0,1,0",
+        "0,waited,0,0,0,0,0,0,0", "0,waited,0,0,0,0,0,1,0", "0,waited,1,0,0,0,0,0,0", "0,waited,1,0,0,0,0,1,0",
+        "0,waited,1,1,0,0,0,0,0", "0,waited,1,1,0,0,0,1,0", "1,failed,0,0,0,0,0,0,0", "1,failed,0,0,0,0,0,1,0",
+        "1,failed,0,0,1,0,0,0,0", "1,failed,0,0,1,0,0,1,0", "1,failed,1,0,0,0,0,0,0", "1,failed,1,0,0,0,0,1,0",
+        "1,failed,1,0,1,0,0,0,0", "1,failed,1,0,1,0,0,1,0", "1,failed,1,1,0,0,0,0,0", "1,failed,1,1,0,0,0,1,0",
+        "1,launched,0,0,0,0,0,0,0", "1,launched,0,0,0,0,0,1,0", "1,launched,1,0,0,0,0,0,0", "1,launched,1,0,0,0,0,1,0",
+        "1,launched,1,1,0,0,0,0,0", "1,launched,1,1,0,0,0,1,0", "1,none,0,0,0,0,0,0,0", "1,none,0,0,0,0,0,1,0",
+        "1,none,0,0,0,1,0,0,0", "1,none,0,0,0,1,0,1,0", "1,waited,0,0,0,0,0,0,0", "1,waited,0,0,0,0,0,1,0",
+        "1,waited,1,0,0,0,0,0,0", "1,waited,1,0,0,0,0,1,0", "1,waited,1,1,0,0,0,0,0", "1,waited,1,1,0,0,0,1,0",
     ),
     "hb_large": (
-        "0,dropped,0,0,0,0,3,0", "0,dropped,0,0,0,0,3,1", "0,failed,0,0,0,0,0,0", "0,failed,0,0,0,0,0,1",
-        "0,failed,0,0,0,0,3,0", "0,failed,0,0,0,0,3,1", "0,failed,0,0,1,0,0,0", "0,failed,0,0,1,0,0,1",
-        "0,failed,0,0,1,0,3,0", "0,failed,0,0,1,0,3,1", "0,failed,1,0,0,0,3,0", "0,failed,1,0,0,0,3,1",
-        "0,failed,1,0,1,0,3,0", "0,failed,1,0,1,0,3,1", "0,failed,1,1,0,0,3,0", "0,failed,1,1,0,0,3,1",
-        "0,launched,0,0,0,0,0,0", "0,launched,0,0,0,0,0,1", "0,launched,0,0,0,0,3,0", "0,launched,0,0,0,0,3,1",
-        "0,launched,1,0,0,0,3,0", "0,launched,1,0,0,0,3,1", "0,launched,1,1,0,0,3,0", "0,launched,1,1,0,0,3,1",
-        "0,none,0,0,0,0,0,0", "0,none,0,0,0,0,0,1", "0,none,0,0,0,1,0,0", "0,none,0,0,0,1,0,1",
-        "0,waited,0,0,0,0,0,0", "0,waited,0,0,0,0,0,1", "0,waited,0,0,0,0,3,0", "0,waited,0,0,0,0,3,1",
-        "0,waited,1,0,0,0,3,0", "0,waited,1,0,0,0,3,1", "0,waited,1,1,0,0,3,0", "0,waited,1,1,0,0,3,1",
-        "1,dropped,0,0,0,0,3,0", "1,dropped,0,0,0,0,3,1", "1,failed,0,0,0,0,0,0", "1,failed,0,0,0,0,0,1",
-        "1,failed,0,0,0,0,3,0", "1,failed,0,0,0,0,3,1", "1,failed,0,0,1,0,0,0", "1,failed,0,0,1,0,0,1",
-        "1,failed,0,0,1,0,3,0", "1,failed,0,0,1,0,3,1", "1,failed,1,0,0,0,3,0", "1,failed,1,0,0,0,3,1",
-        "1,failed,1,0,1,0,3,0", "1,failed,1,0,1,0,3,1", "1,failed,1,1,0,0,3,0", "1,failed,1,1,0,0,3,1",
-        "1,launched,0,0,0,0,0,0", "1,launched,0,0,0,0,0,1", "1,launched,0,0,0,0,3,0", "1,launched,0,0,0,0,3,1",
-        "1,launched,1,0,0,0,3,0", "1,launched,1,0,0,0,3,1", "1,launched,1,1,0,0,3,0", "1,launched,1,1,0,0,3,1",
-        "1,none,0,0,0,0,0,0", "1,none,0,0,0,0,0,1", "1,none,0,0,0,1,0,0", "1,none,0,0,0,1,0,1",
-        "1,waited,0,0,0,0,0,0", "1,waited,0,0,0,0,0,1", "1,waited,0,0,0,0,3,0", "1,waited,0,0,0,0,3,1",
-        "1,waited,1,0,0,0,3,0", "1,waited,1,0,0,0,3,1", "1,waited,1,1,0,0,3,0", "1,waited,1,1,0,0,3,1",
+        "0,dropped,0,0,0,0,3,0,0", "0,dropped,0,0,0,0,3,1,0", "0,failed,0,0,0,0,0,0,0", "0,failed,0,0,0,0,0,1,0",
+        "0,failed,0,0,0,0,3,0,0", "0,failed,0,0,0,0,3,1,0", "0,failed,0,0,1,0,0,0,0", "0,failed,0,0,1,0,0,1,0",
+        "0,failed,0,0,1,0,3,0,0", "0,failed,0,0,1,0,3,1,0", "0,failed,1,0,0,0,3,0,0", "0,failed,1,0,0,0,3,1,0",
+        "0,failed,1,0,1,0,3,0,0", "0,failed,1,0,1,0,3,1,0", "0,failed,1,1,0,0,3,0,0", "0,failed,1,1,0,0,3,1,0",
+        "0,launched,0,0,0,0,0,0,0", "0,launched,0,0,0,0,0,1,0", "0,launched,0,0,0,0,3,0,0", "0,launched,0,0,0,0,3,1,0",
+        "0,launched,1,0,0,0,3,0,0", "0,launched,1,0,0,0,3,1,0", "0,launched,1,1,0,0,3,0,0", "0,launched,1,1,0,0,3,1,0",
+        "0,none,0,0,0,0,0,0,0", "0,none,0,0,0,0,0,1,0", "0,none,0,0,0,1,0,0,0", "0,none,0,0,0,1,0,1,0",
+        "0,waited,0,0,0,0,0,0,0", "0,waited,0,0,0,0,0,1,0", "0,waited,0,0,0,0,3,0,0", "0,waited,0,0,0,0,3,1,0",
+        "0,waited,1,0,0,0,3,0,0", "0,waited,1,0,0,0,3,1,0", "0,waited,1,1,0,0,3,0,0", "0,waited,1,1,0,0,3,1,0",
+        "1,dropped,0,0,0,0,3,0,0", "1,dropped,0,0,0,0,3,1,0", "1,failed,0,0,0,0,0,0,0", "1,failed,0,0,0,0,0,1,0",
+        "1,failed,0,0,0,0,3,0,0", "1,failed,0,0,0,0,3,1,0", "1,failed,0,0,1,0,0,0,0", "1,failed,0,0,1,0,0,1,0",
+        "1,failed,0,0,1,0,3,0,0", "1,failed,0,0,1,0,3,1,0", "1,failed,1,0,0,0,3,0,0", "1,failed,1,0,0,0,3,1,0",
+        "1,failed,1,0,1,0,3,0,0", "1,failed,1,0,1,0,3,1,0", "1,failed,1,1,0,0,3,0,0", "1,failed,1,1,0,0,3,1,0",
+        "1,launched,0,0,0,0,0,0,0", "1,launched,0,0,0,0,0,1,0", "1,launched,0,0,0,0,3,0,0", "1,launched,0,0,0,0,3,1,0",
+        "1,launched,1,0,0,0,3,0,0", "1,launched,1,0,0,0,3,1,0", "1,launched,1,1,0,0,3,0,0", "1,launched,1,1,0,0,3,1,0",
+        "1,none,0,0,0,0,0,0,0", "1,none,0,0,0,0,0,1,0", "1,none,0,0,0,1,0,0,0", "1,none,0,0,0,1,0,1,0",
+        "1,waited,0,0,0,0,0,0,0", "1,waited,0,0,0,0,0,1,0", "1,waited,0,0,0,0,3,0,0", "1,waited,0,0,0,0,3,1,0",
+        "1,waited,1,0,0,0,3,0,0", "1,waited,1,0,0,0,3,1,0", "1,waited,1,1,0,0,3,0,0", "1,waited,1,1,0,0,3,1,0",
     ),
     "deque": (
-        "0,dropped,0,0,0,0,3,0", "0,failed,0,0,0,0,0,0", "0,failed,0,0,0,0,3,0", "0,failed,0,0,1,0,0,0",
-        "0,failed,0,0,1,0,3,0", "0,launched,0,0,0,0,0,0", "0,launched,0,0,0,0,3,0", "0,none,0,0,0,0,0,0",
-        "0,waited,0,0,0,0,0,0", "0,waited,0,0,0,0,3,0", "1,dropped,0,0,0,0,3,0", "1,failed,0,0,0,0,0,0",
-        "1,failed,0,0,0,0,3,0", "1,failed,0,0,1,0,0,0", "1,failed,0,0,1,0,3,0", "1,launched,0,0,0,0,0,0",
-        "1,launched,0,0,0,0,3,0", "1,none,0,0,0,0,0,0", "1,waited,0,0,0,0,0,0", "1,waited,0,0,0,0,3,0",
+        "0,dropped,0,0,0,0,3,0,0", "0,failed,0,0,0,0,0,0,0", "0,failed,0,0,0,0,3,0,0", "0,failed,0,0,1,0,0,0,0",
+        "0,failed,0,0,1,0,3,0,0", "0,launched,0,0,0,0,0,0,0", "0,launched,0,0,0,0,3,0,0", "0,none,0,0,0,0,0,0,0",
+        "0,waited,0,0,0,0,0,0,0", "0,waited,0,0,0,0,3,0,0", "1,dropped,0,0,0,0,3,0,0", "1,failed,0,0,0,0,0,0,0",
+        "1,failed,0,0,0,0,3,0,0", "1,failed,0,0,1,0,0,0,0", "1,failed,0,0,1,0,3,0,0", "1,launched,0,0,0,0,0,0,0",
+        "1,launched,0,0,0,0,3,0,0", "1,none,0,0,0,0,0,0,0", "1,waited,0,0,0,0,0,0,0", "1,waited,0,0,0,0,3,0,0",
     ),
     "shard": (
-        "0,dropped,0,0,0,0,3,0", "0,failed,0,0,0,0,0,0", "0,failed,0,0,0,0,3,0", "0,failed,0,0,1,0,0,0",
-        "0,failed,0,0,1,0,3,0", "0,launched,0,0,0,0,0,0", "0,launched,0,0,0,0,3,0", "0,none,0,0,0,0,0,0",
-        "0,phase1,0,0,0,0,0,0", "0,phase1,0,0,0,0,3,0", "0,waited,0,0,0,0,0,0", "0,waited,0,0,0,0,3,0",
-        "1,dropped,0,0,0,0,3,0", "1,failed,0,0,0,0,0,0", "1,failed,0,0,0,0,3,0", "1,failed,0,0,1,0,0,0",
-        "1,failed,0,0,1,0,3,0", "1,launched,0,0,0,0,0,0", "1,launched,0,0,0,0,3,0", "1,none,0,0,0,0,0,0",
-        "1,phase1,0,0,0,0,0,0", "1,phase1,0,0,0,0,3,0", "1,waited,0,0,0,0,0,0", "1,waited,0,0,0,0,3,0",
+        "0,dropped,0,0,0,0,3,0,0", "0,failed,0,0,0,0,0,0,0", "0,failed,0,0,0,0,3,0,0", "0,failed,0,0,1,0,0,0,0",
+        "0,failed,0,0,1,0,3,0,0", "0,launched,0,0,0,0,0,0,0", "0,launched,0,0,0,0,3,0,0", "0,none,0,0,0,0,0,0,0",
+        "0,none,0,0,0,0,0,0,1",  # marked: the state a mark leaves, whatever it found
+        "0,phase1,0,0,0,0,0,0,0", "0,phase1,0,0,0,0,3,0,0", "0,waited,0,0,0,0,0,0,0", "0,waited,0,0,0,0,3,0,0",
+        "1,dropped,0,0,0,0,3,0,0", "1,failed,0,0,0,0,0,0,0", "1,failed,0,0,0,0,3,0,0", "1,failed,0,0,1,0,0,0,0",
+        "1,failed,0,0,1,0,3,0,0", "1,launched,0,0,0,0,0,0,0", "1,launched,0,0,0,0,3,0,0", "1,none,0,0,0,0,0,0,0",
+        "1,phase1,0,0,0,0,0,0,0", "1,phase1,0,0,0,0,3,0,0", "1,waited,0,0,0,0,0,0,0", "1,waited,0,0,0,0,3,0,0",
     ),
 }
 

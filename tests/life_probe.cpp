@@ -7,9 +7,9 @@
 //   step <kind> <state> <event[:a[:b]]> ...
 //                                  the state after the transitions, in order: stage:accepted | launch:E:window
 //                                  | eager | continue | wait:outcome | commit:deferred:orphans_stay
-//                                  | commit_ran | undone | settled | replaced
+//                                  | commit_ran | undone | settled | replaced | marked | unmarked
 // <kind>: hb (deferred clears, lists) | hb_large (in place, lists) | deque | shard.
-// <state>: staged,pos,win,eager,enospc,cm_pending,undo_E,stale with pos by name.
+// <state>: staged,pos,win,eager,enospc,cm_pending,undo_E,stale,marked with pos by name.
 // Built by tests/test_life.py; it makes no HIP runtime call.
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +46,7 @@ bool parse_kind(const std::string &s, CtxCaps &k) {
 
 bool parse_state(const std::string &s, Life &l) {
     std::istringstream in(s);
-    std::string f[8];
+    std::string f[9];
     for (auto &x : f)
         if (!std::getline(in, x, ',')) return false;
     int pos = -1;
@@ -61,12 +61,13 @@ bool parse_state(const std::string &s, Life &l) {
     l.cm_pending = f[5] == "1";
     l.undo_E = atoi(f[6].c_str());
     l.stale = f[7] == "1";
+    l.marked = f[8] == "1";
     return true;
 }
 
 void print_state(const Life &l) {
-    printf("%d,%s,%d,%d,%d,%d,%d,%d\n", (int)l.staged, kPosNames[(int)l.pos], (int)l.win, (int)l.eager, (int)l.enospc,
-           (int)l.cm_pending, l.undo_E, (int)l.stale);
+    printf("%d,%s,%d,%d,%d,%d,%d,%d,%d\n", (int)l.staged, kPosNames[(int)l.pos], (int)l.win, (int)l.eager, (int)l.enospc,
+           (int)l.cm_pending, l.undo_E, (int)l.stale, (int)l.marked);
 }
 
 template <typename T, size_t N>
@@ -135,6 +136,8 @@ int main() {
                 else if (what == "undone") life_undone(l);
                 else if (what == "settled") life_settled(l);
                 else if (what == "replaced") life_replaced(l);
+                else if (what == "marked") life_lcs_marked(l);
+                else if (what == "unmarked") life_lcs_unmarked(l);
                 else bad = true;
             }
             if (bad) {

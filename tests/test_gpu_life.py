@@ -61,6 +61,7 @@ class Ctx:
 
     # -- clean means
     def reset(self):
+        assert self.lib.fb_log_compact_shard_cancel(self.h) == 0  # (a mark the last call left)
         bad = (np.zeros(1, np.uint8), np.full(1, 1 << 20, np.int32), np.zeros(1, np.int32), np.full(1, NOW))
         assert self.lib.fb_tick_stage(self.h, NOW, 1, *(a.ctypes.data_as(C.c_void_p) for a in bad), None) == _lib.FB_EINVAL
         self.g.load(self.st)
@@ -128,6 +129,19 @@ class Ctx:
             return lib.fb_log_compact(h, -1, None, 0, C.byref(n64))
         if name == "pool_stats":
             return lib.fb_pool_stats(h, NOW, TTE, None, 0, C.byref(_lib.PoolSummary()))
+        if name == "pool_stats_shard":
+            return lib.fb_pool_stats_shard(h, NOW, TTE, None, 0, C.byref(_lib.PoolSummary()), C.byref(n64))
+        if name in ("log_reclaim", "log_reclaim_shard"):  # (an empty prefix: behind the gate nothing is launched)
+            return getattr(lib, "fb_" + name)(h, 0, None, None, None, 0, C.byref(n64))
+        if name == "log_compact_shard_mark":  # (a sharded context checks the bitmap's size ahead of the gate)
+            if self.kind != "shard":
+                return lib.fb_log_compact_shard_mark(h, None, 0, None)
+            view = self.g.compact_exchange()
+            return lib.fb_log_compact_shard_mark(h, C.c_void_p(self.g._cbuf.data_ptr()), view.numel(), None)
+        if name == "log_compact_shard_apply":
+            return lib.fb_log_compact_shard_apply(h, 0, None, 0, None)
+        if name == "log_compact_shard_cancel":
+            return lib.fb_log_compact_shard_cancel(h)
         if name == "exchange_bytes":
             return lib.fb_exchange_bytes(h, 0, C.byref(n64))
         if name == "stage":

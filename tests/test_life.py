@@ -1,6 +1,10 @@
 """The life of a tick (csrc/faasbal_life.h) without a GPU: tests/life_probe.cpp, compiled here,
 answers life_gate and the life_* transitions; tests/life_cases.py is the table -- what the
-library did when ten context flags and one ladder per entry point kept these rules.
+library did when ten context flags and one ladder per entry point kept these rules, and the
+rules of the maintenance calls added since (the pool summaries, the reclaims, a shard group's
+compaction and its `marked` state).  The gate sections of tests/test_pool_stats_shard_host.py,
+test_log_compact_shard_host.py, test_log_reclaim_host.py and test_log_reclaim_shard_host.py
+drive the same probe through _build and _asker below.
 
 1. For every context kind, every state of the table and every call, life_gate refuses with
    the table's message or names the table's duties.
@@ -13,6 +17,7 @@ library did when ten context flags and one ladder per entry point kept these rul
    stand-alone program) and runs clean over the whole table.
 """
 import os
+import re
 import shutil
 import subprocess
 
@@ -135,7 +140,20 @@ def test_no_call_missing(probe):
     hdr = open(os.path.join(REPO, "include", "faasbal.h")).read()
     api = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_api.hip")).read()
     for c in lc.CALLS:
-        assert "Call::%s)" % c in api, c
+        assert re.search(r"enter\(c, [^;]*\bCall::%s\b" % c, api), c
+    # ... and enters by name: no entry point hands enter() a gate of its own making
+    csrc = os.path.join(REPO, "distributed-faas_amd", "csrc")
+    for m in re.finditer(r"^(?:static )?int (fb_\w+|\w+_run)\([^;{]*\{\n(.*?)^\}\n", api, re.M | re.S):
+        args = re.findall(r"\benter\(c, ([^;]*)\)\) return rc_;", m.group(2))
+        assert len(args) == m.group(2).count("enter("), m.group(1)
+        for arg in args:
+            names = re.findall(r"Call::(\w+)", arg)
+            assert names and set(names) <= set(lc.CALLS), (m.group(1), arg)
+            assert re.fullmatch(r"(\w+ \? )?Call::\w+( : Call::\w+)?", arg), (m.group(1), arg)
+    assert len(re.findall(r"\benter\(c, ", api)) >= len(lc.CALLS) - 2  # (the two pairs that share a body)
+    assert len(re.findall(r"\bGate\b[^;\n]*\blife_gate\(", api)) == 1  # enter() itself
+    for f in os.listdir(csrc):
+        assert "life_gate" + "_" not in open(os.path.join(csrc, f)).read(), f  # (a gate beside life_gate)
     for flag in ("c->launched", "c->waited", "c->staged", "c->l_failed", "c->l_eager", "c->l_enospc", "c->phase",
                  "c->cm_pending", "c->stale_any", "c->undo_E", "c->l_win"):
         assert flag not in api, flag
@@ -144,7 +162,7 @@ def test_no_call_missing(probe):
 
 def test_item4_rejected_load_keeps_stale(probe):
     """The one deliberate difference from the old library: a rejected load leaves the Life."""
-    s = "0,none,0,0,0,0,0,1"
+    s = "0,none,0,0,0,0,0,1,0"
     assert s in lc.STATES["hb"]
     refuse, duties, _ = _gate(probe(["gate hb %s load_state" % s])[0])
     assert refuse is None and duties == []
@@ -169,3 +187,7 @@ def test_probe_sanitized(tmp_path):
         reached, _ = walk(ask, kind)
         assert sorted(reached) == sorted(lc.STATES[kind])
         ask(["gate %s %s %s" % (kind, s, c) for s in lc.STATES[kind] for c in lc.CALLS])
+    marked = [s for s in lc.STATES["shard"] if s.endswith(",1")]
+    assert marked == ["0,none,0,0,0,0,0,0,1"] and not any(s.endswith(",1") for k in lc.KINDS[:3] for s in lc.STATES[k])
+    assert ask(["step shard %s %s" % (marked[0], ev) for ev in ("marked", "unmarked", "replaced")]) == \
+        [marked[0], "0,none,0,0,0,0,0,0,0", "0,none,0,0,0,0,0,0,0"]

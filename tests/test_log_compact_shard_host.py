@@ -5,14 +5,15 @@
 2. lcs_plan (csrc/faasbal_layout.h), walked on the CPU by tests/lcs_probe.cpp: the grids cover
    every local entry, every word of the exchange bitmap and every slot exactly once; the
    scratch regions do not overlap and the mark's regions come first.
-3. The gates (csrc/faasbal_life.h, tests/life_lcs_probe.cpp): the mark's and the apply's at every
-   point of a tick's life, on every context kind; "marked" against every existing call; again
-   under the address and undefined-behaviour sanitizers.
+3. The gates (life_gate in csrc/faasbal_life.h, asked of tests/life_probe.cpp): the mark's, the
+   apply's and the cancel's at every point of a tick's life, on every context kind; "marked"
+   against every call.  (tests/test_life.py runs the probe under the sanitizers.)
 4. ShardGroup.compact_log over model ranks, in process and over gloo (world 2): the model's
    result, a wrong ``expect``, a rank whose mark fails.
 5. GpuPushDispatcher over a group of model ranks with a tiny log compacts on the "device".
 """
 import os
+import re
 import shutil
 import socket
 import subprocess
@@ -27,6 +28,7 @@ from faasbal._lib import FB_EHIP, FB_ESTATE, FaasbalError
 from faasbal.sharded import shard_range, split_state
 from lc_model import compact_model
 from shard_model_balancer import ModelRankBalancer
+from test_life import _asker, _build, _gate
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -172,30 +174,20 @@ MARK_STAGED = "fb_log_compact_shard_mark with staged events pending: their seque
 MARK_IN_FLIGHT = "fb_log_compact_shard_mark with a tick in flight: fb_tick_wait first"
 APPLY_ONE_GPU = "fb_log_compact_shard_apply on a one-GPU context: use fb_log_compact"
 APPLY_UNMARKED = "fb_log_compact_shard_apply without fb_log_compact_shard_mark"
-# what touches neither the log nor a tick goes on while a compaction is marked
-MARKED_PASSES = ("exchange_bytes", "debug_read", "sync")
+# what touches neither the log nor a tick goes on while a compaction is marked, and the two calls that end it
+MARKED_PASSES = ("exchange_bytes", "debug_read", "sync", "log_compact_shard_apply", "log_compact_shard_cancel")
+MARK, APPLY, CANCEL, STATS = "log_compact_shard_mark", "log_compact_shard_apply", "log_compact_shard_cancel", "pool_stats_shard"
 
 
-def _ask(exe, lines, env=None):
-    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env)
-    assert p.returncode == 0 and not p.stderr, (p.returncode, p.stderr[-2000:])
-    out = p.stdout.splitlines()
-    assert len(out) == len(lines) and not any(a.startswith("error=") for a in out), p.stdout[-2000:]
-    return out
-
-
-def _gates(exe, lines, env=None):
-    res = []
-    for a in _ask(exe, lines, env):
-        head, refuse = a.split(" refuse=", 1)
-        w = dict(x.split("=", 1) for x in head.split())
-        res.append((None if refuse == "-" else refuse, [] if w["duties"] == "-" else w["duties"].split(",")))
-    return res
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return _asker(_build(tmp_path_factory.mktemp("life_lcs"), "life_probe"))
 
 
 def want_mark(kind, s):
     """The mark's gate, written from the issue's rules on the state's fields."""
-    staged, pos, _, eager, _, cm, undo_e, _ = s.split(",")
+    staged, pos, _, eager, _, cm, undo_e, _, marked = s.split(",")
+    assert marked == "0"
     flush = ["flush"] if cm == "1" else []
     if kind != "shard":
         return MARK_ONE_GPU, flush
@@ -207,18 +199,25 @@ def want_mark(kind, s):
     return None, flush + (["undo"] if int(undo_e) > 0 else []) + (["discard"] if pos in ("waited", "failed") else [])
 
 
-def _check_gates(exe, env=None):
+def test_gates(probe):
+    def gates(lines):
+        return [_gate(a)[:2] for a in probe(lines)]
+
     seen = set()
+    m = "0,none,0,0,0,0,0,0,1"  # marked: the state a mark leaves
+    assert [s for k in lc.KINDS for s in lc.STATES[k] if s.endswith(",1")] == [m]
     for kind in lc.KINDS:
-        states = list(lc.STATES[kind])
-        got = _gates(exe, ["mark %s %s,0" % (kind, s) for s in states], env)
+        states = [s for s in lc.STATES[kind] if s != m]
+        got = gates(["gate %s %s %s" % (kind, s, MARK) for s in states])
         for s, g in zip(states, got):
             assert g == want_mark(kind, s), (kind, s, g)
             seen.add((kind == "shard", s.split(",")[1], g[0], tuple(g[1])))
         # the apply's: only after a mark, only on a sharded context
-        for s, (refuse, duties) in zip(states, _gates(exe, ["apply %s %s,0" % (kind, s) for s in states], env)):
+        for s, (refuse, duties) in zip(states, gates(["gate %s %s %s" % (kind, s, APPLY) for s in states])):
             assert refuse == (APPLY_UNMARKED if kind == "shard" else APPLY_ONE_GPU), (kind, s)
             assert duties == (["flush"] if kind != "shard" and s.split(",")[5] == "1" else []), (kind, s)
+        # the cancel's: open in every state, on every kind, no duties
+        assert gates(["gate %s %s %s" % (kind, s, CANCEL) for s in lc.STATES[kind]]) == [(None, [])] * len(lc.STATES[kind])
     # every position of a tick's life was asked: in flight refused, the others discarded or passed
     assert (True, "waited", None, ("undo", "discard")) in seen and (True, "waited", None, ("discard",)) in seen
     assert (True, "failed", None, ("undo", "discard")) in seen and (True, "dropped", None, ("undo",)) in seen
@@ -228,51 +227,51 @@ def _check_gates(exe, env=None):
     # the transitions: a mark leaves no tick and nothing owed, whatever it found; cancel and
     # apply leave the state a commit leaves
     for s in lc.STATES["shard"]:
+        if s == m:
+            continue
         refuse, duties = want_mark("shard", s)
         if refuse is not None:
             continue
         ev = (["commit_ran"] if "flush" in duties else []) + (["undone"] if "undo" in duties else []) + ["marked"]
-        after = _ask(exe, ["step shard %s,0 %s" % (s, " ".join(ev))], env)[0]
-        assert after == "0,none,0,0,0,0,0,0,1", (s, after)
-    assert _ask(exe, ["step shard 0,none,0,0,0,0,0,0,1 unmarked", "step shard 0,none,0,0,0,0,0,0,1 replaced"], env) == \
-        ["0,none,0,0,0,0,0,0,0"] * 2
-    # marked: the state a mark leaves, against every existing call, a second mark, the apply and
-    # the rank's part of a pool summary
-    m = "0,none,0,0,0,0,0,0,1"
-    for c, (refuse, duties) in zip(lc.CALLS, _gates(exe, ["gate shard %s %s" % (m, c) for c in lc.CALLS], env)):
+        after = probe(["step shard %s %s" % (s, " ".join(ev))])[0]
+        assert after == m, (s, after)
+    assert probe(["step shard %s unmarked" % m, "step shard %s replaced" % m]) == ["0,none,0,0,0,0,0,0,0"] * 2
+    # marked: against every call -- a second mark, the apply, the cancel and the rank's part of a
+    # pool summary among them
+    for c, (refuse, duties) in zip(lc.CALLS, gates(["gate shard %s %s" % (m, c) for c in lc.CALLS])):
         if c in MARKED_PASSES:
             assert (refuse, duties) == (None, []), c
+        elif c == "log_reclaim":  # (it names the wrong context kind first)
+            assert refuse.startswith("fb_log_reclaim on a sharded context") and duties == [], refuse
         else:
             assert (refuse, duties) == (MARKED, []), (c, refuse)
-    assert _gates(exe, ["mark shard " + m, "apply shard " + m, "stats shard " + m], env) == \
-        [(MARKED, []), (None, []), (MARKED, [])]
-    # without a mark the existing calls answer as tests/life_cases.py's table says
-    rows = [(s, c) for s in lc.STATES["shard"] for c in lc.CALLS]
+    assert gates(["gate shard %s %s" % (m, c) for c in (MARK, APPLY, STATS)]) == [(MARKED, []), (None, []), (MARKED, [])]
+    # marked on a one-GPU kind (a point no context reaches): the wrong kind is named first, after the flush
+    for kind in lc.KINDS[:3]:
+        for cm in "01":
+            got = gates(["gate %s 0,none,0,0,0,%s,0,0,1 %s" % (kind, cm, c) for c in (MARK, APPLY)])
+            assert got == [(MARK_ONE_GPU, ["flush"] * int(cm)), (APPLY_ONE_GPU, ["flush"] * int(cm))], (kind, got)
+    # without a mark the calls answer as tests/life_cases.py's table says
+    rows = [(s, c) for s in lc.STATES["shard"] if s != m for c in lc.CALLS]
     by_life = {}
     for r in lc.closure("shard"):
         by_life.setdefault(lc.canon("shard", r), r)
-    for (s, c), g in zip(rows, _gates(exe, ["gate shard %s,0 %s" % (s, c) for s, c in rows], env)):
+    for (s, c), g in zip(rows, gates(["gate shard %s %s" % (s, c) for s, c in rows])):
         assert lc.gate("shard", by_life[s], c) == g, (s, c, g)
-
-
-def test_gates(tmp_path):
-    _check_gates(_hipcc(tmp_path, "life_lcs_probe.cpp", "life_lcs_probe"))
-
-
-def test_gates_sanitized(tmp_path):
-    """Address + undefined-behaviour sanitizers on the host code, as a stand-alone program."""
-    exe = _hipcc(tmp_path, "life_lcs_probe.cpp", "life_lcs_probe_san",
-                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
-    _check_gates(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
 
 
 def test_entry_points_go_through_the_gates():
     api = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_api.hip")).read()
     life = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_life.h")).read()
-    assert "life_gate_log_compact_shard_mark(c->life, c->caps)" in api
-    assert "life_gate_log_compact_shard_apply(c->life, c->caps)" in api
+    for name in ("mark", "apply", "cancel"):
+        body = api[api.index("int fb_log_compact_shard_%s(fb_ctx *c" % name):]
+        body = body[:body.index("\n}\n")]
+        assert "enter(c, Call::log_compact_shard_%s)" % name in body, name
+        assert "X(log_compact_shard_%s)" % name in life and "log_compact_shard_" + name in lc.CALLS
+        # ... ahead of every launch, copy and transition
+        gate = body.index("enter(c, ")
+        assert not re.search(r"launch_|hipMemcpy|life_lcs_|life_replaced", body[:gate]), name
     assert life.count('"%s"' % MARKED) == 1  # stated once
-    assert "X(log_compact_shard" not in life and "log_compact_shard" not in "".join(lc.CALLS)
     hdr = open(os.path.join(REPO, "include", "faasbal.h")).read()
     for name in ("bytes", "mark", "apply", "cancel"):
         assert "int fb_log_compact_shard_%s(" % name in hdr and "fb_log_compact_shard_%s" % name in _lib.EXPORTS

@@ -4,19 +4,21 @@
 2. lr_plan (csrc/faasbal_layout.h), walked on the CPU by tests/lr_probe.cpp and compared with
    the plan recomputed here: the grids cover the prefix [0, min(below_seq, head)) exactly, the
    scratch regions hold what the passes touch and do not overlap.
-3. life_gate_log_reclaim (csrc/faasbal_life.h), walked by tests/life_reclaim_probe.cpp over
-   every point of a tick's life and every context kind; csrc/faasbal_api.hip calls that gate;
+3. life_gate's Call::log_reclaim (csrc/faasbal_life.h), asked of tests/life_probe.cpp over
+   every point of a tick's life and every context kind; csrc/faasbal_api.hip enters through it;
    the library declares, exports and binds the symbol.
 """
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from life_cases import KINDS
 from reclaim_model import inflight_model, live_entries, reclaim_model, slots_mask
+from test_life import _asker, _gate
+from test_life import _build as _build_life
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -116,21 +118,26 @@ def test_plan_is_the_one_recomputed_here(tmp_path):
 
 # --------------------------------------------------------------------------- the gate
 IN_TICK = ("phase1", "launched", "waited", "failed")
+POS = ("none", "phase1", "launched", "waited", "failed", "dropped")
 
 
-def _check_gate(exe, env=None):
-    out = subprocess.run([exe], capture_output=True, text=True, check=True, env=env).stdout
-    rows = []
-    for line in out.splitlines():
-        head, _, refuse = line.partition(" refuse=")
-        r = dict(kv.split("=") for kv in head.split())
-        r["refuse"] = None if refuse == "-" else refuse
-        rows.append(r)
+def test_gate_refusals_and_duties(tmp_path):
+    """Every Pos x staged x kind x cm_pending x undo_E (0, 3), table states or not, with
+    fb_pool_stats' gate at the same point beside it (ps_*).  (That the gate makes no transition
+    needs no row: life_gate takes a const Life &.)"""
+    ask = _asker(_build_life(tmp_path, "life_probe"))
+    rows = [dict(kind=k, staged=st, pos=pos, cm=cm, undo_E=ue) for k in KINDS for st in "01" for pos in POS for cm in "01"
+            for ue in "03"]
+    at = ["%(kind)s %(staged)s,%(pos)s,0,0,0,%(cm)s,%(undo_E)s,0,0" % r for r in rows]
+    for r, mine, ps in zip(rows, ask(["gate %s log_reclaim" % x for x in at]), ask(["gate %s pool_stats" % x for x in at])):
+        refuse, duties, _ = _gate(mine)
+        ps_refuse, ps_duties, _ = _gate(ps)
+        r.update(refuse=refuse, duties=",".join(duties) or "-", ps_duties=",".join(ps_duties) or "-",
+                 ps_refused=str(int(ps_refuse is not None)))
     assert len(rows) == 4 * 2 * 6 * 2 * 2
     assert len({(r["kind"], r["staged"], r["pos"], r["cm"], r["undo_E"]) for r in rows}) == len(rows)
     for r in rows:
         what = str(r)
-        assert r["same_life"] == "1", what  # no transition
         duties = set() if r["duties"] == "-" else set(r["duties"].split(","))
         if r["kind"] == "deque":
             assert r["refuse"] and "deque" in r["refuse"] and duties <= {"flush"}, what
@@ -152,24 +159,17 @@ def _check_gate(exe, env=None):
             assert r["duties"] == r["ps_duties"], what  # fb_pool_stats' duties
 
 
-def test_gate_refusals_and_duties(tmp_path):
-    _check_gate(_build(tmp_path, "life_reclaim_probe.cpp", "life_reclaim_probe"))
-
-
-def test_gate_probe_under_sanitizers(tmp_path):
-    exe = _build(tmp_path, "life_reclaim_probe.cpp", "life_reclaim_probe_san",
-                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
-    _check_gate(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
-
-
 def test_api_calls_the_gate_and_the_binding_knows_the_symbol():
     api = open(os.path.join(CSRC, "faasbal_api.hip")).read()
-    body = api[api.index("int fb_log_reclaim(fb_ctx *c"):]
+    wrapper = api[api.index("int fb_log_reclaim(fb_ctx *c"):]
+    assert "return log_reclaim_run(c, false, " in wrapper[:wrapper.index("\n}\n")]
+    body = api[api.index("static int log_reclaim_run(fb_ctx *c, bool shard"):]
     body = body[:body.index("\n}\n")]
-    assert re.search(r"enter\(c,\s*life_gate_log_reclaim\(c->life,\s*c->caps\)\)", body)
+    assert "enter(c, shard ? Call::log_reclaim_shard : Call::log_reclaim)" in body
     # ... ahead of every launch and every write
-    assert body.index("life_gate_log_reclaim") < body.index("launch_lr_flag") < body.index("launch_lc_scan") \
+    assert body.index("enter(c, ") < body.index("launch_lr_flag") < body.index("launch_lc_scan") \
         < body.index("cap < (int64_t)n") < body.index("launch_lr_take")
+    assert "lr_plan(c->head, below_seq, c->W)" in body and "hipMemcpy" not in body[:body.index("enter(c, ")]
     header = open(os.path.join(REPO, "include", "faasbal.h")).read()
     assert "int fb_log_reclaim(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mask" in header
     from faasbal import _lib

@@ -4,17 +4,16 @@
    tests/reclaim_model.reclaim_model on the global state: lists and log.
 2. lrs_plan (csrc/faasbal_layout.h), walked on the CPU by tests/lrs_probe.cpp and compared
    with the plan recomputed here.
-3. life_gate_log_reclaim_shard (csrc/faasbal_life.h), walked by
-   tests/life_reclaim_shard_probe.cpp over every point of a tick's life, every context kind
-   and a marked compaction, again under the address and undefined-behaviour sanitizers;
-   csrc/faasbal_api.hip enters through it; the library declares, exports and binds the symbol.
+3. life_gate's Call::log_reclaim_shard (csrc/faasbal_life.h), asked of tests/life_probe.cpp
+   over every point of a tick's life, every context kind and a marked compaction (the probe
+   runs under the sanitizers in tests/test_life.py); csrc/faasbal_api.hip enters through it;
+   the library declares, exports and binds the symbol.
 4. ShardGroup.reclaim over model ranks, in process and over gloo (world 2): the model's
    result, a rank that refuses in the count step, a group of ranks without the part.
 5. GpuPushDispatcher's deadline and restart scenarios over a group of reclaiming model ranks
    send what they send over the one-table oracle double.
 """
 import os
-import re
 import shutil
 import socket
 import subprocess
@@ -27,8 +26,11 @@ import lrs_model as lr
 from faasbal import _lib
 from faasbal._lib import FB_EINVAL, FB_ESTATE, FaasbalError
 from faasbal.sharded import shard_range, split_state
+from life_cases import KINDS
 from reclaim_model import reclaim_model, slots_mask
 from shard_model_balancer import ModelRankBalancer
+from test_life import _asker, _gate
+from test_life import _build as _build_life
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -152,21 +154,28 @@ IN_TICK = ("phase1", "launched", "waited", "failed")
 MARKED = "a log compaction is marked: apply or cancel first"
 
 
-def _check_gate(exe, env=None):
-    p = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert p.returncode == 0 and not p.stderr, (p.returncode, p.stderr[-2000:])
-    rows = []
-    for line in p.stdout.splitlines():
-        head, _, refuse = line.partition(" refuse=")
-        r = dict(kv.split("=") for kv in head.split())
-        r["refuse"] = None if refuse == "-" else refuse
-        rows.append(r)
+POS = ("none", "phase1", "launched", "waited", "failed", "dropped")
+
+
+def test_gate_refusals_and_duties(tmp_path):
+    """Every Pos x staged x kind x cm_pending x undo_E (0, 3) x marked, table states or not, with
+    fb_pool_stats_shard's gate at the same point beside it (ps_*).  (That the gate never makes
+    a transition needs no row: life_gate takes a const Life &.)"""
+    ask = _asker(_build_life(tmp_path, "life_probe"))
+    rows = [dict(kind=k, staged=st, pos=pos, cm=cm, undo_E=ue, marked=m) for k in KINDS for st in "01" for pos in POS
+            for cm in "01" for ue in "03" for m in "01"]
+    at = ["%(kind)s %(staged)s,%(pos)s,0,0,0,%(cm)s,%(undo_E)s,0,%(marked)s" % r for r in rows]
+    for r, mine, ps in zip(rows, ask(["gate %s log_reclaim_shard" % x for x in at]),
+                           ask(["gate %s pool_stats_shard" % x for x in at])):
+        refuse, duties, _ = _gate(mine)
+        ps_refuse, ps_duties, _ = _gate(ps)
+        r.update(refuse=refuse, duties=",".join(duties) or "-", ps_duties=",".join(ps_duties) or "-",
+                 ps_refused=str(int(ps_refuse is not None)))
     assert len(rows) == 4 * 2 * 6 * 2 * 2 * 2
     assert len({(r["kind"], r["staged"], r["pos"], r["cm"], r["undo_E"], r["marked"]) for r in rows}) == len(rows)
     seen = set()
     for r in rows:
         what = str(r)
-        assert r["same_life"] == "1", what  # never a transition
         duties = set() if r["duties"] == "-" else set(r["duties"].split(","))
         # refused exactly where fb_pool_stats_shard is, with the same duties
         assert (r["refuse"] is not None) == (r["ps_refused"] == "1"), what
@@ -194,26 +203,18 @@ def _check_gate(exe, env=None):
     assert ("dropped", ("undo",)) in seen and ("dropped", ("flush", "undo")) in seen and ("none", ()) in seen
 
 
-def test_gate_refusals_and_duties(tmp_path):
-    _check_gate(_build(tmp_path, "life_reclaim_shard_probe.cpp", "life_reclaim_shard_probe"))
-
-
-def test_gate_probe_under_sanitizers(tmp_path):
-    """Address + undefined-behaviour sanitizers on the host code, as a stand-alone program."""
-    exe = _build(tmp_path, "life_reclaim_shard_probe.cpp", "life_reclaim_shard_probe_san",
-                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
-    _check_gate(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
-
-
 def test_api_enters_through_the_gate_and_the_binding_knows_the_symbol():
     api = open(os.path.join(CSRC, "faasbal_api.hip")).read()
-    body = api[api.index("int fb_log_reclaim_shard(fb_ctx *c"):]
+    wrapper = api[api.index("int fb_log_reclaim_shard(fb_ctx *c"):]
+    assert "return log_reclaim_run(c, true, " in wrapper[:wrapper.index("\n}\n")]
+    body = api[api.index("static int log_reclaim_run(fb_ctx *c, bool shard"):]
     body = body[:body.index("\n}\n")]
-    assert re.search(r"enter\(c,\s*life_gate_log_reclaim_shard\(c->life,\s*c->caps\)\)", body)
+    assert "enter(c, shard ? Call::log_reclaim_shard : Call::log_reclaim)" in body
     # ... ahead of every launch and every write; the count check before the take
-    assert body.index("life_gate_log_reclaim_shard") < body.index("launch_lr_flag") < body.index("launch_lc_scan") \
+    assert body.index("enter(c, ") < body.index("launch_lr_flag") < body.index("launch_lc_scan") \
         < body.index("cap < (int64_t)n") < body.index("launch_lr_take")
-    assert "lrs_plan(c->head_local, c->W)" in body and "hipMemcpy" not in body[:body.index("life_gate_log_reclaim_shard")]
+    assert "lrs_plan(c->head_local, c->W)" in body and "lr_plan(c->head, below_seq, c->W)" in body
+    assert "hipMemcpy" not in body[:body.index("enter(c, ")]
     # the one-GPU call keeps refusing sharded contexts, and says where to go
     life = open(os.path.join(CSRC, "faasbal_life.h")).read()
     assert "use fb_log_reclaim_shard" in life and life.count('"%s"' % MARKED) == 1

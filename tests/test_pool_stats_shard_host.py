@@ -4,18 +4,16 @@
    pool_stats_model of the whole state, for worlds with empty ranks too; the merge's refusals.
 2. fb_pool_merge (host arithmetic: the library loads without a GPU) equals merge_summaries,
    refusals included.
-3. fb_pool_stats_shard's gate (life_gate_pool_stats_shard, tests/life_shard_probe.cpp): on the
-   sharded kind fb_pool_stats' refusals and duties with the sharded refusal set aside, on the
-   one-GPU kinds a refusal; again under the address and undefined-behaviour sanitizers.
+3. fb_pool_stats_shard's gate (life_gate's Call::pool_stats_shard, asked of tests/life_probe.cpp):
+   on the sharded kind fb_pool_stats' refusals and duties with the sharded refusal set aside, on
+   the one-GPU kinds a refusal.  (tests/test_life.py runs the probe under the sanitizers.)
 4. DistShardGroup's "stats" message over gloo, two processes, model ranks.
 5. GpuPushDispatcher.pool_stats takes a group's summary where the group has one and reads
    the state where it has none.
 """
 import ctypes as C
 import os
-import shutil
 import socket
-import subprocess
 
 import numpy as np
 import pytest
@@ -27,6 +25,7 @@ from faasbal.poolstats import (MAX_EDGES, diff_summary, merge_summaries, pool_st
 from faasbal.sharded import split_state
 from shard_model_balancer import ModelRankBalancer
 from test_gpu_pool_stats import _shape_state
+from test_life import _asker, _build, _gate
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -183,29 +182,15 @@ ONE_GPU_REFUSAL = "fb_pool_stats_shard on a one-GPU context: use fb_pool_stats"
 SHARDED_REFUSAL = "fb_pool_stats on a sharded context: the pool is the group's, a summary needs a collective"
 
 
-def _build_probe(tmp, name, extra=()):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not found: the gate probe cannot be compiled")
-    exe = str(tmp / name)
-    subprocess.run(["hipcc", "-std=c++17", "-O1", *extra, "-I" + os.path.join(REPO, "distributed-faas_amd", "csrc"),
-                    "-I" + os.path.join(REPO, "include"), os.path.join(HERE, "life_shard_probe.cpp"), "-o", exe], check=True)
-    return exe
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return _asker(_build(tmp_path_factory.mktemp("life_ps_shard"), "life_probe"))
 
 
-def _ask(exe, lines, env=None):
-    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env)
-    assert p.returncode == 0 and not p.stderr, (p.returncode, p.stderr[-2000:])
-    out = p.stdout.splitlines()
-    assert len(out) == len(lines) and not any(a.startswith("error=") for a in out), p.stdout[-2000:]
-    res = []
-    for a in out:
-        head, refuse = a.split(" refuse=", 1)
-        w = dict(x.split("=", 1) for x in head.split())
-        res.append((None if refuse == "-" else refuse, [] if w["duties"] == "-" else w["duties"].split(",")))
-    return res
+def test_gate_is_pool_stats_gate_without_the_sharded_refusal(probe):
+    def ask(kind, states):
+        return [_gate(a)[:2] for a in probe(["gate %s %s pool_stats_shard" % (kind, s) for s in states])]
 
-
-def _check_gate(exe, env=None):
     # the sharded kind: every Life the table reaches, every flag state that stands for it
     by_life = {}
     for r in lc.closure("shard"):
@@ -213,39 +198,36 @@ def _check_gate(exe, env=None):
     states = sorted(by_life)
     assert states == sorted(lc.STATES["shard"])
     seen = set()
-    for s, (refuse, duties) in zip(states, _ask(exe, ["gate shard %s" % s for s in states], env)):
+    for s, (refuse, duties) in zip(states, ask("shard", states)):
         for r in by_life[s]:
+            if r.marked:  # between a compaction's mark and its apply both wait
+                assert lc.gate("shard", r, "pool_stats") == (lc.MARKED, []) == (refuse, duties), s
+                continue
             assert lc.gate("shard", r, "pool_stats") == (SHARDED_REFUSAL, [])
             # ... set aside: the ladder of a one-GPU kind with in-place clears, the same flags
             assert lc.gate("deque", r, "pool_stats") == (refuse, duties), (s, r, refuse, duties)
         seen.add((refuse, tuple(duties)))
     # the table has what the test is about: each refusal, a pass, and the undo of a dropped launch
-    assert {m for m, _ in seen} == {None, "fb_pool_stats with staged events pending: launch and commit their tick first",
+    assert {m for m, _ in seen} == {None, lc.MARKED,
+                                    "fb_pool_stats with staged events pending: launch and commit their tick first",
                                     "fb_pool_stats between a tick's wait and its commit: fb_tick_commit first",
                                     "fb_pool_stats with a tick launched: fb_tick_wait and fb_tick_commit first"}
     assert (None, ("undo",)) in seen and (None, ()) in seen
     # one-GPU kinds: refused, whatever the state; at most the flush
     for kind in ("hb", "hb_large", "deque"):
         states = lc.STATES[kind]
-        for s, (refuse, duties) in zip(states, _ask(exe, ["gate %s %s" % (kind, s) for s in states], env)):
+        for s, (refuse, duties) in zip(states, ask(kind, states)):
             assert refuse == ONE_GPU_REFUSAL, (kind, s, refuse)
             assert duties == (["flush"] if s.split(",")[5] == "1" else []), (kind, s, duties)
 
 
-def test_gate_is_pool_stats_gate_without_the_sharded_refusal(tmp_path):
-    _check_gate(_build_probe(tmp_path, "life_shard_probe"))
-
-
-def test_gate_probe_sanitized(tmp_path):
-    """Address + undefined-behaviour sanitizers on the host code, as a stand-alone program."""
-    exe = _build_probe(tmp_path, "life_shard_probe_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
-    _check_gate(exe, dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
-
-
 def test_entry_point_goes_through_the_gate():
     api = open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_api.hip")).read()
-    assert "life_gate_pool_stats_shard(c->life, c->caps)" in api
-    assert "life_gate_pool_stats_shard" in open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_life.h")).read()
+    body = api[api.index("static int pool_stats_run(fb_ctx *c, bool shard"):]
+    body = body[:body.index("\n}\n")]
+    assert "enter(c, shard ? Call::pool_stats_shard : Call::pool_stats)" in body
+    assert body.index("enter(c, ") < body.index("launch_ps_slots") and "hipMemcpy" not in body[:body.index("enter(c, ")]
+    assert "X(pool_stats_shard)" in open(os.path.join(REPO, "distributed-faas_amd", "csrc", "faasbal_life.h")).read()
 
 
 # ------------------------------------------------------------------ 4. the wire format over gloo
