@@ -435,6 +435,10 @@ struct Timer {
 };
 
 static_assert(kMaxR == FB_MAX_ROUNDS && kShardMaxR == FB_MAX_ROUNDS, "the round range include/faasbal.h states");
+static_assert(kEvLeave == FB_EV_LEAVE && kEvDrain == FB_EV_DRAIN && kDrainBias == FB_DRAIN_BIAS &&
+                  kDrainBelow == FB_DRAIN_BELOW && is_draining(FB_DRAIN_BELOW - 1) == FB_IS_DRAINING(FB_DRAIN_BELOW - 1) &&
+                  is_draining(FB_DRAIN_BELOW) == FB_IS_DRAINING(FB_DRAIN_BELOW),
+              "the kinds and the drain mark include/faasbal.h states");
 
 int ensure_table(fb_ctx *c, int R, int nbq) {
     size_t need = (size_t)R * (size_t)nbq;
@@ -2322,7 +2326,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
         // tick commits nothing): the host does not read them at all.  The round table is
         // then sized from the last tick's free counts (a wider one is a rerun away).
         const bool dev_chk = direct && c->caps.lists && c->paths.ev_ll;
-        const uint8_t kmax = c->deque ? FB_EV_OTHER : FB_EV_LEAVE;
+        const bool dq = c->deque;
         auto part = [&](int pi) {
             if (dev_chk) {
                 pbad[pi] = 0;
@@ -2338,7 +2342,7 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
                 const int32_t sl = slot[i], v = val[i];
                 const double t = ts[i];
                 // (a deque context, which never deletes a record, refuses a leave)
-                bad |= (uint32_t)((uint32_t)sl >= Wv) | (uint32_t)(k > kmax) | (uint32_t)!(t <= now) |
+                bad |= (uint32_t)((uint32_t)sl >= Wv) | (uint32_t)!ev_kind_valid(k, dq) | (uint32_t)!(t <= now) |
                        (uint32_t)(t < prev);
                 prev = t;
                 vm = std::max(vm, k <= FB_EV_RECONNECT ? v : 0);
@@ -2364,8 +2368,9 @@ int fb_tick_stage(fb_ctx *c, double now, int32_t n_events, const uint8_t *kind, 
             life_stage(c->life, false);
             c->stage_rec[half] = false;  // nothing was copied out of this half
             if ((uint32_t)slot[i] >= Wv) return fail(c, FB_EINVAL, "event %d: slot %d outside [0, %u)", i, slot[i], Wv);
-            if (kind[i] > FB_EV_LEAVE) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, kind[i]);
+            if (!ev_kind_valid(kind[i], false)) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, kind[i]);
             if (c->deque && kind[i] == FB_EV_LEAVE) return fail(c, FB_EINVAL, "event %d: leave on a deque context", i);
+            if (c->deque && kind[i] == FB_EV_DRAIN) return fail(c, FB_EINVAL, "event %d: drain on a deque context", i);
             if (!(ts[i] <= now) || (i && ts[i] < ts[i - 1]))
                 return fail(c, FB_EINVAL, "event %d: timestamps must be non-decreasing and <= now", i);
         }
@@ -2581,7 +2586,7 @@ static int tick_wait(fb_ctx *c, fb_tick_result *res, Wait &o) {
         const double *ts = (const double *)c->l_chk[2];
         for (int i = 0; i < c->l_E; ++i) {
             if ((uint32_t)sl[i] >= (uint32_t)c->W) return fail(c, FB_EINVAL, "event %d: slot %d outside [0, %d)", i, sl[i], c->W);
-            if (k[i] > FB_EV_LEAVE) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, k[i]);
+            if (!ev_kind_valid(k[i], false)) return fail(c, FB_EINVAL, "event %d: unknown kind %d", i, k[i]);
             if (!(ts[i] <= c->l_now) || (i && ts[i] < ts[i - 1]))
                 return fail(c, FB_EINVAL, "event %d: timestamps must be non-decreasing and <= now", i);
         }

@@ -95,8 +95,18 @@ constexpr int kMaxR = 4096;
 
 // event kinds / status (include/faasbal.h)
 constexpr int kEvRegister = 0, kEvReconnect = 1, kEvHeartbeat = 2, kEvResult = 3, kEvOther = 4,
-              kEvLeave = 5;
+              kEvLeave = 5, kEvDrain = 7;
 constexpr uint8_t kEvsApplied = 0, kEvsReconnect = 1;
+// The kinds a batch may hold, stated once for the host's staging check, the device's check
+// of pinned and device-resident batches (k_ev_link) and the messages that name the first
+// offender: 0..5 and 7 (6 is unassigned); a deque context, which never deletes a record
+// and has no LRU position to take away, takes 0..4.
+constexpr bool ev_kind_valid(int k, bool deque) {
+    return deque ? (k >= 0 && k <= kEvOther) : ((k >= 0 && k <= kEvLeave) || k == kEvDrain);
+}
+// a draining record is marked in its free count (FB_DRAIN_BIAS / FB_IS_DRAINING, include/faasbal.h)
+constexpr int32_t kDrainBias = 1 << 30, kDrainBelow = -(1 << 29);
+constexpr bool is_draining(int32_t free) { return free < kDrainBelow; }
 
 // deque mode (PushDispatcher.start): a committed token rank with this bit set sat in
 // A_L[p:] of the tick that wrote it (final rank = j - x_w), else in A_L[:p] (K_L - x_w + j)

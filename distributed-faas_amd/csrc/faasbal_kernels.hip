@@ -697,14 +697,25 @@ struct SlotRun {
         } else if (!reg) {                               // :356-358 unknown id
             // (not a leave, whose slot holds no record by now: a goodbye creates no worker
             // and asks for no reconnect)
-            if (!leave) {
+            // (nor a drain or a resume: the planned shutdown of nobody is nothing)
+            if (!leave && kind != kEvDrain) {
                 reg = 1; epoch = a.head_in; hb = ts; fr = 0;
                 status = kEvsReconnect;
             }
-        } else if (kind == kEvReconnect) {               // :360-367
-            hb = ts;
-            fr = val;
-            if (val > 0) { inq = 1; qstat = kQsFront; qidx = i; }
+        } else if (kind == kEvReconnect || kind == kEvDrain) {
+            // reconnect (:360-367): hb, free = val, front if val > 0.  The planned shutdown
+            // (include/faasbal.h) shares the branch, for a resume is that front insertion with
+            // the count the record had (a branch of its own behind `result` cost k_ev_apply_ll
+            // 27 more SGPR spills, this form 8: DESIGN.md §5).  The mark rides in the free count,
+            // so a result's free += 1 never reaches 1 and nothing but this branch reads it; the
+            // record, its heartbeat, epoch and in-flight entries stay: not a death
+            const bool rc = kind == kEvReconnect, dr = is_draining(fr), on = val != 0;
+            const int32_t nv = rc ? val : (on ? (dr ? fr : (fr < (1 << 29) - 1 ? fr : (1 << 29) - 1) - kDrainBias)
+                                              : (dr ? fr + kDrainBias : fr));
+            hb = rc ? ts : hb;
+            fr = nv;
+            if (rc ? val > 0 : (!on && dr && nv > 0)) { inq = 1; qstat = kQsFront; qidx = i; }
+            if (!rc && on && !dr) { inq = 0; qstat = kQsOut; }
         } else if (kind == kEvHeartbeat) {               // :370-371
             hb = ts;
         } else if (kind == kEvResult) {                  // :374-387
@@ -966,7 +977,7 @@ __global__ __launch_bounds__(kBS) void k_ev_link(EvArgs a) {
             // heartbeat) for the rest of the launch, whose tick the host then refuses
             const uint8_t k = a.ev_kind[t];
             const double tt = a.ev_ts[t], tp = a.ev_ts[t > 0 ? t - 1 : 0];
-            const bool bad_sk = s >= (uint32_t)a.W || k > kEvLeave;
+            const bool bad_sk = s >= (uint32_t)a.W || !ev_kind_valid(k, false);
             if (bad_sk || !(tt <= a.now) || tt < tp) {
                 a.hout->bad_ev = 1;
                 if (a.cw) a.cw[0] = a.link;

@@ -13,6 +13,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libfaasbal.so")
 
 FB_EV_REGISTER, FB_EV_RECONNECT, FB_EV_HEARTBEAT, FB_EV_RESULT, FB_EV_OTHER, FB_EV_LEAVE = 0, 1, 2, 3, 4, 5
+FB_EV_DRAIN = 7  # (6 is unassigned); val != 0 drains, val == 0 resumes
+# a draining record is marked in its free count (include/faasbal.h): draining iff free < FB_DRAIN_BELOW,
+# true free count = free + FB_DRAIN_BIAS
+FB_DRAIN_BIAS, FB_DRAIN_BELOW = 1 << 30, -(1 << 29)
 FB_EVS_APPLIED, FB_EVS_RECONNECT, FB_EVS_UNKNOWN = 0, 1, 2
 FB_OK, FB_EINVAL, FB_ENOMEM, FB_EHIP, FB_ERANGE, FB_ENOSPC, FB_ESTATE, FB_ERERUN = 0, -1, -2, -3, -4, -5, -6, -7
 ERRNAMES = {FB_EINVAL: "FB_EINVAL", FB_ENOMEM: "FB_ENOMEM", FB_EHIP: "FB_EHIP", FB_ERANGE: "FB_ERANGE",

@@ -106,6 +106,14 @@ def _arr(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+def draining_of(st, base=0):
+    """dict(slot, free) of the draining records in a read_state() dict: slots (plus ``base``)
+    ascending, int32, and their true free counts."""
+    free = np.asarray(st["free"], np.int32)
+    idx = np.nonzero(np.asarray(st["reg"]).astype(bool) & (free < _lib.FB_DRAIN_BELOW))[0]
+    return {"slot": (idx + int(base)).astype(np.int32), "free": free[idx] + np.int32(_lib.FB_DRAIN_BIAS)}
+
+
 class GpuBalancer:
     """Device-resident worker table + LRU queue + in-flight log on one GPU.
 
@@ -234,6 +242,13 @@ class GpuBalancer:
         if with_log:
             out["log"] = log[: loglen.value]
         return out
+
+    def draining(self):
+        """The draining workers of the committed state (FB_EV_DRAIN, include/faasbal.h):
+        dict(slot, free) -- the slots that hold a record with ``free < FB_DRAIN_BELOW``,
+        ascending, and their true free counts (``free + FB_DRAIN_BIAS``).  From one state
+        read without the log: draining sets are small and rare."""
+        return draining_of(self.read_state(with_log=False))
 
     def inflight(self):
         """Per-slot count of in-flight log entries (committed state; one-GPU heartbeat)."""

@@ -46,24 +46,32 @@ import time
 import numpy as np
 
 from . import codec
-from ._lib import FB_ENOSPC, FB_ESTATE, FB_EVS_RECONNECT, FaasbalError
+from ._lib import FB_DRAIN_BELOW, FB_DRAIN_BIAS, FB_ENOSPC, FB_ESTATE, FB_EVS_RECONNECT, FaasbalError
 from .balancer import GpuBalancer
 from .poolstats import pool_stats_model
 
 EV_REGISTER, EV_RECONNECT, EV_HEARTBEAT, EV_RESULT, EV_OTHER, EV_LEAVE = 0, 1, 2, 3, 4, 5
 # {"type": "leave"}: a worker's goodbye (FB_EV_LEAVE, include/faasbal.h); the reference's workers never send it
+# {"type": "drain"} / {"type": "resume"}: the planned shutdown -- no new tasks, the ones in flight finish -- and its
+# undo (FB_EV_DRAIN with val 1 / 0, include/faasbal.h); the reference's workers never send them either
+EV_DRAIN = 7
 _KINDS = {"register": EV_REGISTER, "reconnect": EV_RECONNECT, "heartbeat": EV_HEARTBEAT, "result": EV_RESULT,
-          "leave": EV_LEAVE}
+          "leave": EV_LEAVE, "drain": EV_DRAIN, "resume": EV_DRAIN}
+_NO_SLOT = ("leave", "drain", "resume")  # messages that never allocate a slot (_drop_unknown_leaves)
 _I32 = (-(1 << 31), (1 << 31) - 1)
 
 
 class WorkerView:
     """Read-only stand-in for ``PushDispatcher.PushWorker`` (``:203-212``)."""
 
-    __slots__ = ("free_processes", "last_heartbeat", "time_to_expire")
+    __slots__ = ("free_processes", "last_heartbeat", "time_to_expire", "draining")
 
     def __init__(self, free_processes, last_heartbeat, time_to_expire):
-        self.free_processes = int(free_processes)
+        # a draining record carries its mark in the device's free count (FB_IS_DRAINING): the
+        # view shows the true count and the mark as an attribute
+        free_processes = int(free_processes)
+        self.draining = free_processes < FB_DRAIN_BELOW
+        self.free_processes = free_processes + FB_DRAIN_BIAS if self.draining else free_processes
         self.last_heartbeat = float(last_heartbeat)
         self.time_to_expire = time_to_expire
 
@@ -87,13 +95,20 @@ class GpuPushDispatcher:
     again (fb_log_reclaim).  ``max_attempts`` (None: no bound): a task taken back that
     many times is recorded FAILED instead.  With both None the loop makes no call,
     Redis command or message it did not make before.
+
+    ``evict_drained``: when true, a draining identity (``drain()``, or a worker's own
+    ``{"type": "drain"}``) whose tasks in flight have all come back gets a synthetic
+    ``leave`` at the top of the next tick: its record is deleted and its identity released,
+    and nothing is dispatched again because nothing was in flight.  With no drain ever
+    sent the loop is unchanged whatever the flag.
     """
 
     def __init__(self, ip_address, port, time_to_expire=10, *, max_workers=65536, max_inflight=1 << 24,
                  max_events=65536, device=0, redis_client=None, subscriber=None, socket=None, poller=None,
                  clock=time.time, tasks_channel="tasks", batch_io=True, balancer=None, task_timeout=None,
-                 max_attempts=None):
+                 max_attempts=None, evict_drained=False):
         self.port = port
+        self.evict_drained = bool(evict_drained)
         self.batch_io = bool(batch_io)
         self.ip_address = ip_address
         self.time_to_expire = time_to_expire
@@ -185,6 +200,9 @@ class GpuPushDispatcher:
         self.head = 0                                  # in-flight log length
         self._last_ts = -np.inf
         self._leaving = collections.deque()            # identities evict() asked to remove, for the next tick
+        self._drain_ops = collections.deque()          # (identity, "drain" | "resume") of drain() / resume(), likewise
+        self._draining = {}                            # slot whose record is draining (the device's mark, mirrored)
+                                                       # -> its tasks in flight, counted down as they come back
         self._marks = collections.deque()              # (log head after a tick that dispatched, its clock), ascending
         self.attempts = {}                             # task_id -> times it was taken back from a live worker
 
@@ -257,9 +275,20 @@ class GpuPushDispatcher:
 
     def _drain_inbound(self):
         msgs = []
+        if self.evict_drained and self._draining:
+            # drained dry: every task that was in flight has come back, so the goodbye orphans nothing
+            # (one goodbye each: a leave still waiting behind a full batch is not queued again)
+            dry = [self.identity[s] for s, n in self._draining.items() if n == 0]
+            if dry:
+                waiting = set(self._leaving)
+                self._leaving.extend(w for w in dry if w not in waiting)
         # the operator's goodbyes (evict()) ahead of this tick's ZMQ messages
         while self._leaving and len(msgs) < self.max_events:
             msgs.append((self._leaving.popleft(), {"type": "leave"}, self._stamp()))
+        # ... then the operator's drains and resumes (drain(), resume())
+        while self._drain_ops and len(msgs) < self.max_events:
+            wid, typ = self._drain_ops.popleft()
+            msgs.append((wid, {"type": typ}, self._stamp()))
         while len(msgs) < self.max_events and self._inbound_ready():
             worker_id, message = self.receive_message()
             msgs.append((worker_id, message, self._stamp()))
@@ -300,12 +329,13 @@ class GpuPushDispatcher:
     def _drop_unknown_leaves(self, msgs):
         """A leave from an identity without a slot -- none before the tick and no earlier
         message in the batch that gives it one -- is dropped: no slot means no record, so
-        there is nothing to delete, and a goodbye must not allocate a slot."""
+        there is nothing to delete, and a goodbye must not allocate a slot.  The same for a
+        drain and a resume: no record, nothing to mark."""
         keep, new = [], set()
         for x in msgs:
             wid, m, _t = x
             if wid not in self.slot_of and wid not in new:
-                if isinstance(m, dict) and m.get("type") == "leave":
+                if isinstance(m, dict) and m.get("type") in _NO_SLOT:
                     continue
                 new.add(wid)
             keep.append(x)
@@ -323,6 +353,35 @@ class GpuPushDispatcher:
         self._leaving.extend(worker_ids)
         return [w for w in worker_ids if w in self.slot_of]
 
+    def drain(self, worker_ids):
+        """Stop giving these workers tasks and let them finish what they have (a rolling
+        deploy, a cordoned node, a shrinking pool): a synthetic ``{"type": "drain"}`` per
+        identity, applied by the next tick ahead of its ZMQ messages, as ``evict()``'s leaves
+        are and behind them.  The records stay, results keep being written, heartbeats keep
+        them alive, nothing is dispatched a second time; ``draining()`` counts their tasks
+        down, and ``evict_drained`` lets them go at zero.  Returns the identities that had a
+        slot (the others' messages are dropped)."""
+        worker_ids = list(worker_ids)
+        self._drain_ops.extend((w, "drain") for w in worker_ids)
+        return [w for w in worker_ids if w in self.slot_of]
+
+    def resume(self, worker_ids):
+        """Undo ``drain()``: a synthetic ``{"type": "resume"}`` per identity.  A worker with
+        free processes is back first in line, as after a ``reconnect``."""
+        worker_ids = list(worker_ids)
+        self._drain_ops.extend((w, "resume") for w in worker_ids)
+        return [w for w in worker_ids if w in self.slot_of]
+
+    def draining(self):
+        """The draining identities -> their tasks in flight, from the host's in-flight table
+        (counted when the drain is seen, then down with every task that comes back)."""
+        return {self.identity[s]: n for s, n in self._draining.items()}
+
+    def _gone(self, s):
+        """An entry of slot s left the in-flight table: one task less on a draining worker."""
+        if s in self._draining:
+            self._draining[s] -= 1
+
     def _take_back(self, seqs):
         """The host's half of a reclaim: the sequences (ascending) leave the in-flight
         table, every task counts an attempt; below ``max_attempts`` it goes to the front of
@@ -336,6 +395,8 @@ class GpuPushDispatcher:
                 raise FaasbalError(FB_ESTATE, "the device reclaimed sequence %d, which the in-flight table lacks" % q)
             tid = ent[0]
             self.task_seq.pop(tid, None)
+            if self._draining:
+                self._gone(ent[1])
             n = self.attempts.get(tid, 0) + 1
             tids.append(tid)
             if self.max_attempts is not None and n >= self.max_attempts:
@@ -404,7 +465,7 @@ class GpuPushDispatcher:
         arrived = msgs
         unknown = []
         if self.mode == "deque":
-            msgs, unknown = self._deque_filter(msgs)  # (register and result only: a leave is ignored)
+            msgs, unknown = self._deque_filter(msgs)  # (register and result only: a leave, a drain and a resume are ignored)
         else:
             msgs = self._drop_unknown_leaves(msgs)
         E = len(msgs)
@@ -413,17 +474,23 @@ class GpuPushDispatcher:
         val = np.zeros(E, np.int32)
         ts = np.empty(E, np.float64)
         seq = np.full(E, -1, np.int64)
+        drains = False
         for i, (wid, m, t) in enumerate(msgs):
             typ = m.get("type") if isinstance(m, dict) else None
             k = _KINDS.get(typ, EV_OTHER)
             kind[i] = k
             slot[i] = self._slot(wid)
             ts[i] = t
+            if k == EV_DRAIN:
+                val[i] = 1 if typ == "drain" else 0
+                drains = True
             if k == EV_REGISTER or k == EV_RECONNECT:
                 v = int(m["data"]["num_processes" if k == EV_REGISTER else "free_processes"])
                 if not (_I32[0] <= v <= _I32[1]):
                     raise FaasbalError(-1, "process count %d does not fit int32" % v)
                 val[i] = v
+                if v < FB_DRAIN_BELOW:  # (a count that reads as the mark: the mirror follows the count)
+                    drains = True
             elif k == EV_RESULT:
                 seq[i] = self.task_seq.get(m["data"]["task_id"], -1)
         # a one-GPU balancer hands the tick's assignments back in compact form -- slot and
@@ -478,6 +545,8 @@ class GpuPushDispatcher:
                 if q >= 0 and self.inflight.get(q, (None, -1))[1] == slot[i]:
                     tid, _ = self.inflight.pop(q)
                     self.task_seq.pop(tid, None)
+                    if self._draining:
+                        self._gone(int(slot[i]))
                     if self.attempts:
                         self.attempts.pop(tid, None)
         if rpipe is not None:
@@ -485,8 +554,10 @@ class GpuPushDispatcher:
         # ---- redistribution: orphans (ascending old sequence) go first
         orphan_tids = []
         for q in out["orphans"]:
-            tid, _ = self.inflight.pop(int(q))
+            tid, s = self.inflight.pop(int(q))
             self.task_seq.pop(tid, None)
+            if self._draining:
+                self._gone(s)
             orphan_tids.append(tid)
         if orphan_tids:
             self.pending.extendleft(reversed(orphan_tids))
@@ -528,10 +599,39 @@ class GpuPushDispatcher:
         # ---- evicted records: their identities become unknown (:246-249)
         for s in out["evicted"]:
             self._release(int(s))
+        if drains or self._draining:
+            self._mirror_drains(kind, slot, val, status, out["evicted"])
         self.ticks += 1
         if self.stats_every > 0 and self.ticks % self.stats_every == 0:
             self.publish_stats()
         return res
+
+    def _mirror_drains(self, kind, slot, val, status, evicted):
+        """The device's mark (FB_IS_DRAINING of the free count, include/faasbal.h) mirrored
+        message by message: a drain sets it; a resume ends it; a register or a reconnect
+        overwrites the count, so the mark is whatever the new count says; a leave or an
+        unknown sender (the record deleted, or created anew with free = 0) ends it, and so
+        does an eviction.  A slot newly marked gets its tasks counted, once, from the
+        in-flight table as this tick leaves it (a draining worker is dispatched nothing)."""
+        was = set(self._draining)
+        now = set(was)
+        for i in range(len(kind)):
+            k, s = int(kind[i]), int(slot[i])
+            if status[i] == FB_EVS_RECONNECT or k == EV_LEAVE:
+                now.discard(s)
+            elif k == EV_DRAIN:
+                (now.add if val[i] else now.discard)(s)
+            elif k == EV_REGISTER or k == EV_RECONNECT:
+                (now.add if val[i] < FB_DRAIN_BELOW else now.discard)(s)
+        now.difference_update(int(s) for s in evicted)
+        for s in was - now:
+            del self._draining[s]
+        new = now - was
+        if new:
+            self._draining.update(dict.fromkeys(new, 0))
+            for _tid, s in self.inflight.values():
+                if s in new:
+                    self._draining[s] += 1
 
     def start_heartbeat(self, max_ticks=None):
         """The dispatcher loop (``task_dispatcher.py:324-419``), one tick per pass."""
@@ -563,6 +663,7 @@ class GpuPushDispatcher:
         gone = [self.identity[int(s)] for s in out["evicted"]]
         for s in out["evicted"]:
             self._release(int(s))
+            self._draining.pop(int(s), None)
         return gone
 
     # ------------------------------------------------------- state / inspection
@@ -706,6 +807,11 @@ class GpuPushDispatcher:
         self.head = len(st["log"])
         self._marks = collections.deque((int(h), float(t)) for h, t in st.get("marks", ()))
         self.attempts = {tid: int(n) for tid, n in st.get("attempts", {}).items()}
+        # the draining set from the loaded free counts: the mark travels in the state itself
+        self._draining = dict.fromkeys((int(s) for s in np.nonzero(reg.astype(bool) & (free < FB_DRAIN_BELOW))[0]), 0)
+        for _tid, s in self.inflight.values():
+            if s in self._draining:
+                self._draining[s] += 1
 
 
 def ShardedPushDispatcher(ip_address, port, time_to_expire=10, *, max_workers=65536, max_inflight=1 << 24,

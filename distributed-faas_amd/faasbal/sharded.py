@@ -22,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .balancer import GpuBalancer, _arr, _p
+from .balancer import GpuBalancer, _arr, _p, draining_of
 from ._lib import FB_ERERUN, FaasbalError
 from .poolstats import HISTS, SCALARS, merge_summaries
 
@@ -208,6 +208,10 @@ class ShardedBalancer(GpuBalancer):
             out["log_seq"] = seq[: n.value]
         out["base"] = self.base
         return out
+
+    def draining(self):
+        """This rank's draining workers (``GpuBalancer.draining``), slots global."""
+        return draining_of(self.read_state(with_log=False), self.base)
 
     # ----------------------------------------------------------------- ticks
     def launch(self, *a, **k):
@@ -395,6 +399,12 @@ class ShardGroup:
 
     def read_state(self, with_log=True):
         return merge_states(self._each("read", with_log=with_log), self.n_workers_global)
+
+    def draining(self):
+        """The group's draining workers (``GpuBalancer.draining``'s dict, slots global): every
+        rank's own, from its state read without the log, merged in rank order."""
+        parts = [draining_of(st, st["base"]) for st in self._each("read", with_log=False)]
+        return {k: np.concatenate([p[k] for p in parts]).astype(np.int32) for k in ("slot", "free")}
 
     def tick(self, now, tte, ev_kind=(), ev_slot=(), ev_val=(), ev_ts=(), ev_seq=None, n_pending=0):
         k = np.asarray(ev_kind, np.uint8)

@@ -46,6 +46,8 @@ extern "C" {
 /* Inbound message kinds (task_dispatcher.py:347-387). */
 #define FB_EV_REGISTER 0   /* {"type":"register","data":{"num_processes":n}}   */
 #define FB_EV_RECONNECT 1  /* {"type":"reconnect","data":{"free_processes":n}} */
+/* (Both overwrite the free count, so they end a drain, FB_EV_DRAIN below: a restarted
+ * worker is a fresh worker.) */
 #define FB_EV_HEARTBEAT 2  /* {"type":"heartbeat"}                              */
 #define FB_EV_RESULT 3     /* {"type":"result", ...}; seq = task's log sequence */
 #define FB_EV_OTHER 4      /* any other type: ignored for known workers         */
@@ -73,6 +75,46 @@ extern "C" {
  *   - Deque contexts (no liveness, records never deleted) refuse a batch that holds a
  *     leave at stage: FB_EINVAL, "event %d: leave on a deque context", nothing staged. */
 #define FB_EV_LEAVE 5
+/* (Kind 6 is unassigned and refused as an unknown kind.) */
+/* {"type":"drain"} / {"type":"resume"}: the planned shutdown (absent from the reference):
+ * "give me no new work, let me finish what I have".  val != 0 drains, val == 0 resumes;
+ * seq is ignored.  There is no new persistent state: a draining record is marked in its
+ * free count, which every kernel, load, read, snapshot, summary, compaction and reclaim
+ * carries as the opaque int32 it always was.  A record is draining iff
+ * FB_IS_DRAINING(free); its true free count is free + FB_DRAIN_BIAS.  A result does
+ * free += 1 and queues the worker only at free == 1, so a draining worker never comes
+ * back into the LRU queue by itself.  One drain at clock ts from slot s:
+ *   - Purge first.  The purge at ts runs before it, as before every message.
+ *   - s holds no record at that point (it never had one, it expired at ts, it left):
+ *     nothing happens.  No record is created and no reconnect is asked for.  The evicted
+ *     list keeps its rule: a touched slot without a record after the tick is listed, as
+ *     for a leave.
+ *   - s holds a record that is not draining, val != 0:
+ *     free = min(free, (1 << 29) - 1) - FB_DRAIN_BIAS, and the slot is out of the LRU
+ *     queue.  Nothing else changes: the record, its heartbeat (the operator may have sent
+ *     the message, not the worker), its epoch and its in-flight entries stay.  It is not a
+ *     death: nothing is orphaned.  The clamp keeps an absurd count inside the draining
+ *     range (a count above 2^29 - 1 resumes as 2^29 - 1; one below -(1 << 29) already reads
+ *     as draining and is outside what this message supports).
+ *   - s already draining, val != 0: nothing changes.
+ *   - Resume (val == 0) of a draining record: free += FB_DRAIN_BIAS; if that is > 0 the
+ *     slot goes to the front of the LRU queue exactly as a reconnect(n > 0) puts it there.
+ *     Of a record that is not draining: nothing.
+ *   - The status is FB_EVS_APPLIED in every case.
+ *   - Later messages of s, in the tick or after it: a result completes its entry, does
+ *     free += 1, updates the heartbeat and never queues the slot; a heartbeat is a
+ *     heartbeat; register(n) and reconnect(n) overwrite free and so end the drain; an
+ *     expired heartbeat or a leave deletes the record as ever, and its live entries are
+ *     orphans as ever.
+ *   - fb_read_inflight of s is unchanged by a drain or a resume.
+ *   - After any tick the committed state is the one fb_load_state installs from
+ *     fb_read_state's arrays: the bias travels in free_processes.
+ *   - Deque contexts refuse a batch that holds a drain at stage: FB_EINVAL,
+ *     "event %d: drain on a deque context", nothing staged. */
+#define FB_EV_DRAIN 7
+#define FB_DRAIN_BIAS (1 << 30)
+#define FB_DRAIN_BELOW (-(1 << 29))
+#define FB_IS_DRAINING(free) ((free) < FB_DRAIN_BELOW)
 
 /* Per-event status written by a tick. */
 #define FB_EVS_APPLIED 0
@@ -288,7 +330,8 @@ int fb_log_reclaim_shard(fb_ctx *ctx, int64_t below_seq, const uint8_t *slot_mas
  * (its pool is the group's, which needs a collective: fb_pool_stats_shard on every rank, then
  * fb_pool_merge), and out of order.  A refused call changes nothing.
  * Replaces nothing in the reference, which keeps no such view: its only look at the pool is
- * the per-worker is_alive walk of purge_workers (task_dispatcher.py:241-249). */
+ * the per-worker is_alive walk of purge_workers (task_dispatcher.py:241-249).
+ * Draining workers (FB_EV_DRAIN) are counted in free_hist[0] and add nothing to free_total. */
 #define FB_PS_FREE_BINS 33
 #define FB_PS_MAX_EDGES 15
 typedef struct fb_pool_summary {
