@@ -17,7 +17,10 @@ collective is issued on too, so kernels and collective are ordered on-device.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
+from collections import namedtuple
 
 import numpy as np
 
@@ -217,6 +220,17 @@ class ShardedBalancer(GpuBalancer):
     def launch(self, *a, **k):
         """Phase 1.  Afterwards all-reduce ``exchange()`` (SUM) over the ranks, then ``cont()``."""
         super().launch(*a, **k)
+        self._launched()
+
+    def purge_launch(self, now, tte):
+        """Phase 1 of this rank's share of a purge: no events, nothing dispatched; the
+        exchange and ``cont()`` follow as for a tick."""
+        self._E = 0
+        self._chk(self.lib.fb_purge_launch(self.h, float(now), float(tte)))
+        self._launched()
+
+    def _launched(self):
+        # the launch's exchange size, asked once: exchange() is a view of that many bytes
         n = C.c_int64()
         self._chk(self.lib.fb_exchange_bytes(self.h, self._E, C.byref(n)))
         self._xbytes = n.value
@@ -242,40 +256,27 @@ class ShardedBalancer(GpuBalancer):
             raise FaasbalError(_lib.FB_ESTATE, "sharded context: use local_assignments() (or set_full_assign)")
         return super().assignments(first, n)
 
-    def _allreduce(self, allreduce):
-        n = C.c_int64()
-        self._chk(self.lib.fb_exchange_bytes(self.h, self._E, C.byref(n)))
-        self._xbytes = n.value
-        with self.torch.cuda.stream(self.stream):
-            if allreduce is None:
-                # issued on self.stream; the explicit wait orders phase 2 after it on that
-                # stream (RCCL) or after its completion (gloo)
-                self.torch.distributed.all_reduce(self.exchange(), async_op=True).wait()
-            else:
-                allreduce(self.exchange())
+    def tick_outputs(self, res):
+        """A waited tick's outputs: the whole tick's assignments where this rank writes them
+        (set_full_assign), else this rank's own (task, slot) pairs."""
+        out = dict(result=res)
+        if getattr(self, "full_assign", False):
+            out.update(assign=self.assignments())
+        else:
+            task, slot = self.local_assignments()
+            out.update(task=task, slot=slot)
+        out.update(reconnect=self.event_status(), orphans=self.orphans(), evicted=self.evicted())
+        return out
 
-    def _run_phases(self, launch, allreduce):
-        """Phase 1, the exchange, phase 2 and the wait -- again with a wider round table
-        while the tick asks for it (FB_ERERUN: the same tick, relaunched; every rank
-        gets the same answer, so the ranks' collectives stay matched)."""
-        for attempt in range(MAX_RELAUNCH + 1):
-            launch()
-            self._allreduce(allreduce)
-            self.cont()
-            try:
-                return self.wait()
-            except FaasbalError as e:
-                if e.code != FB_ERERUN or attempt == MAX_RELAUNCH:
-                    raise
+    def purge_outputs(self, res):
+        return dict(result=res, evicted=self.evicted(), orphans=self.orphans())
 
     def purge(self, now, tte, commit=True, allreduce=None):
         """This rank's share of ``purge_workers`` (``task_dispatcher.py:241-249``):
         the exchange and phase 2 run as for a tick, nothing is dispatched; returns
         dict(result, evicted, orphans) of this rank's slots and log shard."""
-        self._E = 0
-        res = self._run_phases(lambda: self._chk(self.lib.fb_purge_launch(self.h, float(now), float(tte))),
-                               allreduce)
-        out = dict(result=res, evicted=self.evicted(), orphans=self.orphans())
+        res = run_phases([self], lambda b: b.purge_launch(now, tte), functools.partial(dist_reduce, allreduce=allreduce))
+        out = self.purge_outputs(res[0])
         if commit:
             self.commit()
         return out
@@ -283,21 +284,51 @@ class ShardedBalancer(GpuBalancer):
     def tick(self, now, tte, ev_kind=(), ev_slot=(), ev_val=(), ev_ts=(), ev_seq=None, n_pending=0,
              commit=True, outputs=True, allreduce=None):
         """One sharded tick; ``allreduce(tensor)`` defaults to torch.distributed.all_reduce (SUM)."""
-        res = self._run_phases(lambda: self.launch(now, tte, ev_kind, ev_slot, ev_val, ev_ts, ev_seq, n_pending),
-                               allreduce)
-        out = dict(result=res)
-        if outputs:
-            # the whole tick's assignments where this rank writes them (set_full_assign), else
-            # this rank's own (task, slot) pairs
-            if getattr(self, "full_assign", False):
-                out.update(assign=self.assignments())
-            else:
-                task, slot = self.local_assignments()
-                out.update(task=task, slot=slot)
-            out.update(reconnect=self.event_status(), orphans=self.orphans(), evicted=self.evicted())
+        res = run_phases([self], lambda b: b.launch(now, tte, ev_kind, ev_slot, ev_val, ev_ts, ev_seq, n_pending),
+                         functools.partial(dist_reduce, allreduce=allreduce))
+        out = self.tick_outputs(res[0]) if outputs else dict(result=res[0])
         if commit:
             self.commit()
         return out
+
+
+def run_phases(bals, launch, reduce):
+    """A tick or purge on the ranks this process holds: phase 1 on each (``launch(rank)``),
+    the exchanges summed over the group (``reduce(ranks, tensors)``), phase 2 and the wait --
+    again with a wider round table while the tick asks for it (FB_ERERUN: the same tick,
+    relaunched; every rank gets the same answer, so the ranks' collectives stay matched).
+    Every rank waits even after one failed (a rerun request reaches them all).  Returns the
+    ranks' results, nothing committed; raises the first rank's failure."""
+    for attempt in range(MAX_RELAUNCH + 1):
+        for b in bals:
+            launch(b)
+        reduce(bals, [b.exchange() for b in bals])
+        for b in bals:
+            b.cont()
+        res, err = [], None
+        for b in bals:
+            try:
+                res.append(b.wait())
+            except FaasbalError as e:
+                err = err or e
+        if err is None:
+            return res
+        if err.code != FB_ERERUN or attempt == MAX_RELAUNCH:
+            raise err
+
+
+def dist_reduce(bals, xs, allreduce=None):
+    """torch.distributed's SUM, in place, of each held rank's uint8 tensor -- or the caller's
+    ``allreduce(tensor)`` --, issued on the rank's stream where it has one: the explicit wait
+    orders what follows after it on that stream (RCCL) or after its completion (gloo)."""
+    for b, x in zip(bals, xs):
+        stream = getattr(b, "stream", None)
+        with (b.torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            if allreduce is None:
+                import torch.distributed as dist
+                dist.all_reduce(x, async_op=True).wait()
+            else:
+                allreduce(x)
 
 
 def merge_states(states, n_workers):
@@ -322,14 +353,15 @@ def merge_states(states, n_workers):
 class ShardGroup:
     """A worker table sharded over ranks, behind GpuBalancer's tick API -- what
     GpuPushDispatcher drives (``balancer=``), so the drop-in's host loop, message
-    flow and Redis I/O are the same for one GPU and for N.  Subclasses say how a
-    call reaches the ranks: in this process (LocalShardGroup) or over
-    torch.distributed from rank 0 (DistShardGroup)."""
+    flow and Redis I/O are the same for one GPU and for N.  Subclasses say which ranks
+    this process holds and how they meet the others (the transport): all of them, in this
+    process (LocalShardGroup), or rank 0 of a torch.distributed group (DistShardGroup)."""
 
     mode = "heartbeat"
 
-    def __init__(self, n_workers, rank_balancers=()):
+    def __init__(self, n_workers, rank_balancers, transport):
         self.n_workers_global = int(n_workers)
+        self.bals, self.transport = list(rank_balancers), transport
         # rank balancers (those this process holds) without a part of the summary, such as
         # test doubles: no device summary, and GpuPushDispatcher.pool_stats reads the state
         if not all(callable(getattr(b, "pool_stats_part", None)) for b in rank_balancers):
@@ -342,7 +374,14 @@ class ShardGroup:
             self.reclaim = None
 
     def _each(self, op, **kw):  # -> list of per-rank results, rank order
-        raise NotImplementedError
+        self.transport.announce(op, kw)
+        outs, bad = _OPS[op].run(self.transport, self.bals, op, kw)
+        if bad is not None:
+            code, msg = bad
+            if code is None:
+                raise RuntimeError("shard operation %r failed on a rank: %s" % (op, msg))
+            raise FaasbalError(code, "shard operation %r failed on a rank: %s" % (op, msg))
+        return outs
 
     def pool_stats(self, now, tte, age_edges=()):
         """The group's pool summary (``GpuBalancer.pool_stats``' dict): every rank's part,
@@ -440,215 +479,130 @@ def merge_reclaimed(parts):
     return {"n": int(len(seq)), "seq": seq[order], "slot": slot[order]}
 
 
-def _guarded(f, *a):
+# ------------------------------------------------------------------ the group's protocols
+# Every process of a group runs the same function for an operation -- rank 0's group,
+# serve_shard on the other ranks, the group that holds every rank -- over the ranks it holds
+# (``bals``) and a transport that says how those meet the others.  Each returns (the per-rank
+# results in rank order where rank 0 is held, else None; the first failure or None).
+
+def _guarded(f, *a, **k):
+    """f's value as (True, value), its failure as (False, (code, message)) instead of raised:
+    every rank must still reach the group's next collective, and the group raises the failure
+    once every rank has answered."""
     try:
-        return (True, f(*a))
-    except Exception as e:  # noqa: BLE001 -- the group raises it once every rank has answered
-        return (False, _failure(e))
+        return (True, f(*a, **k))
+    except Exception as e:  # noqa: BLE001
+        return (False, (getattr(e, "code", None), "%s: %s" % (type(e).__name__, e)))
+
+
+def _first_bad(flags):
+    return next((f[1] for f in flags if not f[0]), None)
+
+
+def _call(tp, bals, op, kw):
+    """A plain call (load, read, stats) on every rank, the parts brought together."""
+    outs = tp.agree([_guarded(_OPS[op].call, b, kw) for b in bals], _OPS[op].reply)
+    bad = _first_bad(outs)
+    return (None, bad) if bad is not None else ([o[1] for o in outs], None)
 
 
 def serve_op(bal, op, kw, allreduce=None, commit=True):
-    """One group operation on this rank's balancer (every rank runs the same op).
-    ``commit=False`` leaves a tick / purge waited but uncommitted (DistShardGroup
-    commits only once every rank has succeeded)."""
-    if op == "load":
-        bal.load(kw["st"])
-        return None
-    if op == "read":
-        return bal.read_state(with_log=kw["with_log"])
-    if op == "tick":
-        out = bal.tick(kw["now"], kw["tte"], kw["ev_kind"], kw["ev_slot"], kw["ev_val"], kw["ev_ts"], kw["ev_seq"],
-                       kw["n_pending"], allreduce=allreduce, commit=commit)
-        return out
-    if op == "purge":
-        return bal.purge(kw["now"], kw["tte"], allreduce=allreduce, commit=commit)
-    if op == "stats":  # (reads only: nothing to commit, nothing to settle)
-        return bal.pool_stats_part(kw["now"], kw["tte"], kw["age_edges"])
-    if op == "compact":  # (a collective of its own: mark, reduce, agree, apply or cancel)
-        import torch.distributed as dist
-        out, bad = _compact_rank(dist, _dev(dist), bal, kw, allreduce)
-        if bad is not None:
-            _raise_bad(op, bad)
-        return out
-    if op == "reclaim":  # (an agreement of its own: count, agree, take)
-        import torch.distributed as dist
-        out, bad = _reclaim_rank(dist, _dev(dist), bal, kw)
-        if bad is not None:
-            _raise_bad(op, bad)
-        return out
-    raise ValueError("unknown group operation %r" % op)
+    """One group operation as the rank balancer's own call (``_OPS[op].call``), raised, not
+    guarded.  ``commit=False`` leaves a tick / purge waited but uncommitted."""
+    call = _OPS[op].call
+    return call(bal, kw, allreduce=allreduce, commit=commit) if _OPS[op].run is _tick else call(bal, kw)
 
 
-def _raise_bad(op, bad):
-    code, msg = bad
-    if code is None:
-        raise RuntimeError("shard operation %r failed on a rank: %s" % (op, msg))
-    raise FaasbalError(code, "shard operation %r failed on a rank: %s" % (op, msg))
+def rank_phases(bal, op, kw, allreduce=None):
+    """A rank's own tick / purge, waited and not committed, guarded."""
+    return _guarded(serve_op, bal, op, kw, allreduce, False)
 
 
-def _failure(e):
-    return (getattr(e, "code", None), "%s: %s" % (type(e).__name__, e))
+def _tick(tp, bals, op, kw):
+    """A tick or purge: the phases on the held ranks (run_phases), one header per rank
+    agreed on, and only when every rank succeeded the commit -- so the shards never diverge
+    -- and the ranks' lists to the group's caller."""
+    outs = tp.phases(bals, op, kw)
+    heads = tp.agree(outs, _TICK_HEAD)
+    bad = _first_bad(heads)
+    if bad is not None:
+        return None, bad
+    for b in bals:
+        b.commit()
+    return tp.collect([o[1] for o in outs], [h[1] for h in heads], _TICK_LISTS), None
 
 
 def _compact_verdict(marks, expect):
     """(the group's live count, the first failure or None) from every rank's guarded mark."""
-    bad = next((m[1] for m in marks if not m[0]), None)
+    bad = _first_bad(marks)
     total = sum(int(m[1]) for m in marks if m[0])
     if bad is None and expect >= 0 and expect != total:
         bad = (_lib.FB_ESTATE, "the group's log holds %d live entries, the caller expected %d" % (total, expect))
     return total, bad
 
 
-def _compact_reduce(bal, x, allreduce):
-    """The bitmap all-reduced in place, on the rank's stream where it has one (as a tick's exchange)."""
-    import contextlib
-    stream = getattr(bal, "stream", None)
-    with (bal.torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-        if allreduce is None:
-            import torch.distributed as dist
-            dist.all_reduce(x, async_op=True).wait()
-        else:
-            allreduce(x)
-
-
-def _gather_flags(dist, dev, ok, err, word=0):
-    """One fixed header per rank, all-gathered: (ok, code, word).  Returns, on every rank, the
-    list of (ok, word | (code, message)) in rank order; messages follow pickled only when a
-    rank failed, as for ticks."""
-    import torch
-    world = dist.get_world_size()
-    h = torch.zeros(_HDR, dtype=torch.int64)
-    h[0] = 1 if ok else 0
-    h[1] = 0 if ok or err[0] is None else int(err[0])
-    h[2] = int(word)
-    hs = [torch.zeros(_HDR, dtype=torch.int64, device=dev) for _ in range(world)]
-    dist.all_gather(hs, h.to(dev))
-    hs = [x.cpu().numpy() for x in hs]
-    if all(x[0] for x in hs):
-        return [(True, int(x[2])) for x in hs]
-    msgs = [None] * world
-    dist.all_gather_object(msgs, None if ok else err)
-    return [(True, int(x[2])) if x[0] else (False, msgs[i]) for i, x in enumerate(hs)]
-
-
-def _compact_rank(dist, dev, bal, kw, allreduce=None):
-    """A group compaction on this rank (every rank runs it): mark, the bitmap's all-reduce --
-    which a rank whose mark failed joins with zeros of the agreed size, so that no rank blocks
-    in the collective --, one header all-gather of the ranks' ok flags and live counts, then
-    every rank applies or every rank cancels.  Rank 0 asks for the kept list.  Returns
-    (this rank's compact_apply result or None, the first failure or None)."""
-    try:
-        mark = (True, bal.compact_mark())
-    except Exception as e:  # noqa: BLE001 -- reported to rank 0, which raises it
-        mark = (False, _failure(e))
-    x = bal.compact_exchange(zeroed=not mark[0])
-    if x.numel():
-        _compact_reduce(bal, x, allreduce)
-    marks = _gather_flags(dist, dev, mark[0], None if mark[0] else mark[1], mark[1] if mark[0] else 0)
-    total, bad = _compact_verdict(marks, kw["expect"])
-    out = None
+def _compact(tp, bals, op, kw):
+    """A group compaction: mark, the bitmaps reduced -- a rank whose mark failed joins with
+    zeros of the agreed size, so that no rank blocks in the collective --, the ranks' ok
+    flags and live counts agreed on, then every rank applies (rank 0 asks for the kept list)
+    and they agree again, or every rank cancels: nothing has changed anywhere."""
+    marks = [_guarded(b.compact_mark) for b in bals]
+    xs = [b.compact_exchange(zeroed=not m[0]) for b, m in zip(bals, marks)]
+    if xs[0].numel():
+        tp.reduce(bals, xs)
+    total, bad = _compact_verdict(tp.agree(marks, _WORD), kw["expect"])
     if bad is None:
-        try:
-            done = (True, bal.compact_apply(total, bool(kw["want_kept"]) and dist.get_rank() == 0))
-        except Exception as e:  # noqa: BLE001
-            done = (False, _failure(e))
+        done = [_guarded(b.compact_apply, total, bool(kw["want_kept"]) and r == 0) for r, b in zip(tp.ranks, bals)]
         # (the count gives every rank the same verdict; what is left is a rank's own runtime error)
-        flags = _gather_flags(dist, dev, done[0], None if done[0] else done[1])
-        bad = next((f[1] for f in flags if not f[0]), None)
-        out = done[1] if done[0] else None
+        bad = _first_bad(tp.agree([(ok, 0 if ok else v) for ok, v in done], _WORD))
     if bad is not None:
-        bal.compact_cancel()
-    return out, bad
+        for b in bals:
+            b.compact_cancel()
+        return None, bad
+    return [d[1] for d in done], None
 
 
-def _reclaim_rank(dist, dev, bal, kw):
-    """A group reclaim on this rank (every rank runs it): count, one header all-gather of the
-    ranks' ok flags and counts -- when a rank refused nothing has changed anywhere, and no rank
-    takes --, take, a second header (a take that fails now is the rank's own runtime error),
-    then the lists to rank 0 as one padded byte tensor per rank, 12 bytes per entry (the
-    sequences, then the slots).  Returns (rank 0: the ranks' dict(n, seq, slot) in rank order;
-    the others: None, the first failure or None)."""
-    import torch
-    rank, world = dist.get_rank(), dist.get_world_size()
-    cnt = _guarded(bal.reclaim_part, kw["below_seq"], kw["slots"], True)
-    flags = _gather_flags(dist, dev, cnt[0], None if cnt[0] else cnt[1], cnt[1]["n"] if cnt[0] else 0)
-    bad = next((f[1] for f in flags if not f[0]), None)
+def _reclaim(tp, bals, op, kw):
+    """A group reclaim: every rank counts -- every refusal it would make, with nothing changed
+    anywhere -- and the counts are agreed on; only when all of them can do the ranks take, and
+    agree again (a take that fails now, or takes another number than it counted, is the rank's
+    own runtime error); then the lists to the group's caller."""
+    args = (kw["below_seq"], kw["slots"])
+    counts = tp.agree([_guarded(lambda b: b.reclaim_part(*args, True)["n"], b) for b in bals], _WORD)
+    bad = _first_bad(counts)
     if bad is not None:
         return None, bad
-    done = _guarded(bal.reclaim_part, kw["below_seq"], kw["slots"])
-    if done[0] and done[1]["n"] != flags[rank][1]:
-        done = (False, (_lib.FB_ESTATE, "rank %d counted %d entries to reclaim and took %d"
-                        % (rank, flags[rank][1], done[1]["n"])))
-    after = _gather_flags(dist, dev, done[0], None if done[0] else done[1])
-    bad = next((f[1] for f in after if not f[0]), None)
+    done = [_guarded(b.reclaim_part, *args) for b in bals]
+    for i, r in enumerate(tp.ranks):
+        if done[i][0] and done[i][1]["n"] != counts[r][1]:
+            done[i] = (False, (_lib.FB_ESTATE, "rank %d counted %d entries to reclaim and took %d"
+                               % (r, counts[r][1], done[i][1]["n"])))
+    bad = _first_bad(tp.agree([(ok, 0 if ok else v) for ok, v in done], _WORD))
     if bad is not None:
         return None, bad
-    counts = [int(f[1]) for f in flags]
-    mx = max(counts[1:], default=0)
-    parts = [done[1]] + [dict(n=0, seq=np.zeros(0, np.int64), slot=np.zeros(0, np.int32)) for _ in range(world - 1)]
-    if mx > 0:
-        mine = torch.zeros(12 * mx, dtype=torch.uint8)
-        if rank != 0 and counts[rank]:
-            payload = np.concatenate([np.ascontiguousarray(done[1]["seq"], np.int64).view(np.uint8),
-                                      np.ascontiguousarray(done[1]["slot"], np.int32).view(np.uint8)])
-            mine[:len(payload)] = torch.from_numpy(payload)
-        bufs = [torch.zeros(12 * mx, dtype=torch.uint8, device=dev) for _ in range(world)] if rank == 0 else None
-        dist.gather(mine.to(dev), bufs, dst=0)
-        if rank == 0:
-            for i in range(1, world):
-                b, n = bufs[i].cpu().numpy(), counts[i]
-                parts[i] = dict(n=n, seq=b[:8 * n].view(np.int64).copy(), slot=b[8 * n:12 * n].view(np.int32).copy())
-    return (parts if rank == 0 else None), None
+    return tp.collect([d[1] for d in done], [c[1] for c in counts], _RECLAIM_LISTS), None
 
 
-def _serve_guarded(bal, op, kw):
-    """serve_op on this rank, its failure returned instead of raised: every rank must
-    still reach the group's gather (a rank that skipped it would leave the others
-    blocked in the collective).  A tick / purge is not committed here."""
-    try:
-        return (True, serve_op(bal, op, kw, commit=False))
-    except Exception as e:  # noqa: BLE001 -- reported to rank 0, which raises it
-        return (False, (getattr(e, "code", None), "%s: %s" % (type(e).__name__, e)))
-
-
-def _settle(bal, op, outs):
-    """After the gather, on every rank: commit a tick / purge only when it succeeded
-    on every rank (so the shards never diverge); returns the first failure or None."""
-    bad = next((o[1] for o in outs if not o[0]), None)
-    if bad is None and op in ("tick", "purge"):
-        bal.commit()
-    return bad
-
-
-# DistShardGroup's wire format per call: a fixed header tensor broadcast from rank 0
-# (operation, event count, tasks, clock), then for ticks / purges the event batch packed
-# into one byte tensor (25 B per message), and back a fixed header per rank (all
-# gathered: every rank commits only when all succeeded) plus one padded byte tensor
-# per rank gathered to rank 0 (tasks, slots, orphans, evicted).  Loads and state reads
-# (not per tick) and failure messages travel as pickled objects.
-# A pool summary ("stats") travels as tensors too: the call header carries the number of
-# age edges in the event count's word and the clock and tte in theirs, the edges follow as
-# one float64 tensor when there are any, and every rank's part comes back as one fixed
-# int64 record (an ok flag, a code, the queue's length, then fb_pool_summary's words in
-# the struct's order, doubles as bit patterns), all-gathered so that every rank sees every
-# flag; only when a rank failed do the messages follow, pickled, as for ticks.
-# A log compaction ("compact") is a header alone: the caller's expected live count (-1: none)
-# in the event count's word, whether rank 0 wants the kept list in the tasks' word.  Its
-# payload is the live bitmap, all-reduced in place like a tick's exchange; one fixed header
-# per rank (ok flag, code, live count) is all-gathered before the apply and one after it.
-# A reclaim ("reclaim") travels as tensors as well, since with task_timeout it can run at the
-# top of every tick: the call header carries below_seq in the event count's word and the number
-# of slots in the tasks' word (-1: no mask), the global slots follow as one int32 tensor when
-# there are any; one fixed header per rank (ok flag, code, count) is all-gathered after the
-# count step and one after the take, and the lists come back as one padded byte tensor per rank
-# gathered to rank 0, 12 bytes per entry (the int64 sequences, then the int32 slots); pickled
-# messages follow only when a rank failed.
-_OP_CODES = {"tick": 1, "purge": 2, "load": 3, "read": 4, "stop": 5, "stats": 6, "compact": 7, "reclaim": 8}
-_OP_NAMES = {v: k for k, v in _OP_CODES.items()}
+# ------------------------------------------------------------------ the wire format
+# A call is a fixed header of _HDR int64 words broadcast from rank 0 -- the operation's code,
+# then the words its _OPS entry states (clocks as bit patterns) -- and the entry's payload
+# tensor when it has elements.  What comes back is the protocol's: fixed records all-gathered
+# (agree), byte lists gathered to rank 0 (collect), the exchange all-reduced in place (reduce).
+# Loads and state reads (not per tick) travel pickled both ways, and so do failure messages.
 _HDR = 8  # int64 words of the call header / the per-rank result header
 _PS_WORDS = C.sizeof(_lib.PoolSummary) // 8  # fb_pool_summary's words (SCALARS' order, then HISTS')
 _PS_REC = 3 + _PS_WORDS
 _PS_DOUBLES = ("oldest_hb", "newest_hb")
+_PICKLED = "pickled"
+_TICK_ARGS = ("now", "tte", "ev_kind", "ev_slot", "ev_val", "ev_ts", "ev_seq", "n_pending")
+
+
+def _bits(x):
+    return int(np.float64(x).view(np.int64))
+
+
+def _real(w):
+    return float(np.int64(w).view(np.float64))
 
 
 def _pack_summary(part, queue_len):
@@ -669,12 +623,8 @@ def _unpack_summary(rec):
     return part, int(rec[2])
 
 
-def _dev(dist):
-    import torch
-    return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-
-
 def _pack_events(kw):
+    """A tick's event batch as one byte array, 25 B per message."""
     k = np.ascontiguousarray(kw["ev_kind"], np.uint8)
     parts = [k.view(np.uint8), np.ascontiguousarray(kw["ev_slot"], np.int32).view(np.uint8),
              np.ascontiguousarray(kw["ev_val"], np.int32).view(np.uint8),
@@ -690,39 +640,95 @@ def _unpack_events(buf, E):
                 ev_seq=buf[o[4]:o[5]].view(np.int64).copy())
 
 
-def _bcast_call(dist, dev, op, kw):
+# what agree() carries per rank: ok, a code, then ``pack(value)`` in a record of ``width`` words
+_Record = namedtuple("_Record", "width pack unpack")
+_WORD = _Record(_HDR, lambda n: (int(n),), lambda w: int(w[0]))  # a count
+_STATS = _Record(_PS_REC, lambda v: _pack_summary(*v)[2:], lambda w: _unpack_summary(np.concatenate([[1, 0], w])))
+# a tick's / purge's result: the rank's counts, then the lengths of its lists (no tasks travel:
+# rank 0 writes the whole assignment array itself, fb_set_full_assign)
+_TICK_HEAD = _Record(_HDR, lambda out: (int(out["result"].get("n_local", 0)), int(out["result"].get("n_orphans_local", 0)),
+                                        int(out["result"]["n_evicted"]), 0, len(out["orphans"]), len(out["evicted"])),
+                     lambda w: w.copy())
+
+# what collect() carries per rank: ``nbytes(agreed value)`` bytes of ``pack(value)``
+_Lists = namedtuple("_Lists", "nbytes pack unpack")
+_TICK_LISTS = _Lists(  # the orphans (int64), then the evicted slots (int32): a few KB
+    lambda h: 8 * int(h[4]) + 4 * int(h[5]),
+    lambda out: np.concatenate([np.ascontiguousarray(out["orphans"], np.int64).view(np.uint8),
+                                np.ascontiguousarray(out["evicted"], np.int32).view(np.uint8)]),
+    lambda h, b: dict(result=dict(n_local=int(h[0]), n_orphans_local=int(h[1]), n_evicted=int(h[2])),
+                      orphans=b[:8 * int(h[4])].view(np.int64).copy(),
+                      evicted=b[8 * int(h[4]):8 * int(h[4]) + 4 * int(h[5])].view(np.int32).copy(), reconnect=None))
+_RECLAIM_LISTS = _Lists(  # 12 bytes per entry: the sequences (int64), then the slots (int32)
+    lambda n: 12 * n,
+    lambda part: np.concatenate([np.ascontiguousarray(part["seq"], np.int64).view(np.uint8),
+                                 np.ascontiguousarray(part["slot"], np.int32).view(np.uint8)]),
+    lambda n, b: dict(n=n, seq=b[:8 * n].view(np.int64).copy(), slot=b[8 * n:12 * n].view(np.int32).copy()))
+
+
+class _Op:
+    """One group operation.  ``head(kw)``: the call header's words 1..; ``payload``: None,
+    _PICKLED (kw travels pickled) or (dtype, its element count from the header, its elements
+    from kw); ``kw(header, payload)``: the receiver's kw; ``run``: the protocol; ``call``: the
+    rank balancer's own call; ``reply``: a plain call's record (None: pickled); ``launch`` /
+    ``outputs``: a tick's or purge's phase 1 and outputs, for run_phases."""
+
+    def __init__(self, code, run=None, head=lambda kw: (), payload=None, kw=lambda h, p: {}, call=None, reply=None,
+                 launch=None, outputs=None):
+        self.code, self.run, self.head, self.payload, self.kw, self.call = code, run, head, payload, kw, call
+        self.reply, self.launch, self.outputs = reply, launch, outputs
+
+
+_OPS = {
+    "tick": _Op(1, _tick,
+                head=lambda kw: (len(kw["ev_kind"]), kw["n_pending"], _bits(kw["now"]), _bits(kw["tte"])),
+                payload=(np.uint8, lambda h: 25 * h[1], _pack_events),
+                kw=lambda h, p: dict(now=_real(h[3]), tte=_real(h[4]), n_pending=int(h[2]), **_unpack_events(p, int(h[1]))),
+                call=lambda b, kw, **how: b.tick(*[kw[k] for k in _TICK_ARGS], **how),
+                launch=lambda b, kw: b.launch(*[kw[k] for k in _TICK_ARGS]),
+                outputs=lambda b, res: b.tick_outputs(res)),
+    "purge": _Op(2, _tick,
+                 head=lambda kw: (0, 0, _bits(kw["now"]), _bits(kw["tte"])),
+                 kw=lambda h, p: dict(now=_real(h[3]), tte=_real(h[4])),
+                 call=lambda b, kw, **how: b.purge(kw["now"], kw["tte"], **how),
+                 launch=lambda b, kw: b.purge_launch(kw["now"], kw["tte"]),
+                 outputs=lambda b, res: b.purge_outputs(res)),
+    "load": _Op(3, _call, payload=_PICKLED, call=lambda b, kw: b.load(kw["st"])),
+    "read": _Op(4, _call, payload=_PICKLED, call=lambda b, kw: b.read_state(with_log=kw["with_log"])),
+    "stop": _Op(5),  # (the header is the whole call; serve_shard returns)
+    "stats": _Op(6, _call,  # (reads only: nothing to commit)
+                 head=lambda kw: (len(kw["age_edges"]), 0, _bits(kw["now"]), _bits(kw["tte"])),
+                 payload=(np.float64, lambda h: h[1], lambda kw: kw["age_edges"]),
+                 kw=lambda h, p: dict(now=_real(h[3]), tte=_real(h[4]), age_edges=p),
+                 call=lambda b, kw: b.pool_stats_part(kw["now"], kw["tte"], kw["age_edges"]), reply=_STATS),
+    "compact": _Op(7, _compact,  # (the header is the whole call; -1: no expected count)
+                   head=lambda kw: (kw["expect"], 1 if kw["want_kept"] else 0),
+                   kw=lambda h, p: dict(expect=int(h[1]), want_kept=bool(h[2]))),
+    "reclaim": _Op(8, _reclaim,  # (-1 slots: no mask)
+                   head=lambda kw: (kw["below_seq"], -1 if kw["slots"] is None else len(kw["slots"])),
+                   payload=(np.int32, lambda h: h[2], lambda kw: kw["slots"]),
+                   kw=lambda h, p: dict(below_seq=int(h[1]), slots=None if h[2] < 0 else p)),
+}
+_OP_NAMES = {spec.code: op for op, spec in _OPS.items()}
+
+
+def _dev(dist):
+    import torch
+    return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+
+
+def _send_call(dist, dev, op, kw):
     """Rank 0: the call to every rank.  Returns nothing; the ranks read it with _recv_call."""
     import torch
-    h = torch.zeros(_HDR, dtype=torch.int64)
-    h[0] = _OP_CODES[op]
-    if op in ("tick", "purge"):
-        E = len(kw.get("ev_kind", ())) if op == "tick" else 0
-        h[1] = E
-        h[2] = int(kw.get("n_pending", 0))
-        h[3] = int(np.float64(kw["now"]).view(np.int64))
-        h[4] = int(np.float64(kw["tte"]).view(np.int64))
-    elif op == "stats":
-        h[1] = len(kw["age_edges"])
-        h[3] = int(np.float64(kw["now"]).view(np.int64))
-        h[4] = int(np.float64(kw["tte"]).view(np.int64))
-    elif op == "compact":  # (the header is the whole call)
-        h[1] = int(kw["expect"])
-        h[2] = 1 if kw["want_kept"] else 0
-    elif op == "reclaim":
-        h[1] = int(kw["below_seq"])
-        h[2] = -1 if kw["slots"] is None else len(kw["slots"])
-    dist.broadcast(h.to(dev), src=0)
-    if op in ("tick", "purge"):
-        if int(h[1]):
-            dist.broadcast(torch.from_numpy(_pack_events(kw)).to(dev), src=0)
-    elif op == "stats":
-        if int(h[1]):
-            dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["age_edges"], np.float64)).to(dev), src=0)
-    elif op == "reclaim":
-        if int(h[2]) > 0:
-            dist.broadcast(torch.from_numpy(np.ascontiguousarray(kw["slots"], np.int32)).to(dev), src=0)
-    elif op not in ("stop", "compact"):
+    spec = _OPS[op]
+    h = np.zeros(_HDR, np.int64)
+    words = (spec.code,) + tuple(spec.head(kw))
+    h[:len(words)] = words
+    dist.broadcast(torch.from_numpy(h).to(dev), src=0)
+    if spec.payload == _PICKLED:
         dist.broadcast_object_list([kw], src=0)
+    elif spec.payload is not None and spec.payload[1](h) > 0:
+        dist.broadcast(torch.from_numpy(np.ascontiguousarray(spec.payload[2](kw), spec.payload[0])).to(dev), src=0)
 
 
 def _recv_call(dist, dev):
@@ -732,306 +738,157 @@ def _recv_call(dist, dev):
     dist.broadcast(h, src=0)
     h = h.cpu().numpy()
     op = _OP_NAMES[int(h[0])]
-    if op == "compact":
-        return op, dict(expect=int(h[1]), want_kept=bool(h[2]))
-    if op == "reclaim":
-        slots = None
-        if int(h[2]) >= 0:
-            slots = torch.zeros(int(h[2]), dtype=torch.int32, device=dev)
-            if int(h[2]):
-                dist.broadcast(slots, src=0)
-            slots = slots.cpu().numpy()
-        return op, dict(below_seq=int(h[1]), slots=slots)
-    if op == "stats":
-        edges = torch.zeros(int(h[1]), dtype=torch.float64, device=dev)
-        if int(h[1]):
-            dist.broadcast(edges, src=0)
-        return op, dict(now=float(h[3:4].view(np.float64)[0]), tte=float(h[4:5].view(np.float64)[0]),
-                        age_edges=edges.cpu().numpy())
-    if op not in ("tick", "purge"):
-        if op == "stop":
-            return op, {}
+    spec, p = _OPS[op], None
+    if spec.payload == _PICKLED:
         box = [None]
         dist.broadcast_object_list(box, src=0)
         return op, box[0]
-    E = int(h[1])
-    kw = dict(now=float(h[3:4].view(np.float64)[0]), tte=float(h[4:5].view(np.float64)[0]), n_pending=int(h[2]))
-    if op == "tick":
-        if E:
-            buf = torch.empty(25 * E, dtype=torch.uint8, device=dev)
-            dist.broadcast(buf, src=0)
-            kw.update(_unpack_events(buf.cpu().numpy(), E))
+    if spec.payload is not None:
+        p = torch.from_numpy(np.zeros(max(int(spec.payload[1](h)), 0), spec.payload[0])).to(dev)
+        if p.numel():
+            dist.broadcast(p, src=0)
+        p = p.cpu().numpy()
+    return op, spec.kw(h, p)
+
+
+# ------------------------------------------------------------------ the transports
+class InProcess:
+    """Every rank of the group in this process (one GPU, or rank contexts on several
+    devices): nothing travels; the exchange is summed on the device -- the reduction RCCL
+    performs across GPUs, byte for byte (one contributor per byte)."""
+
+    def __init__(self, world):
+        self.ranks = range(world)
+
+    def announce(self, op, kw):
+        pass
+
+    def agree(self, flags, record):
+        return flags
+
+    def collect(self, vals, heads, lists):
+        return vals
+
+    def reduce(self, bals, xs):
+        sync = bals[0].torch.cuda.synchronize if xs[0].is_cuda else (lambda: None)
+        sync()
+        total = xs[0].clone()
+        for x in xs[1:]:
+            total += x
+        for x in xs:
+            x.copy_(total)
+        sync()
+
+    def phases(self, bals, op, kw):
+        """The ranks' phases in step; a failure is every rank's (none of them commits)."""
+        ok, res = _guarded(run_phases, bals, lambda b: _OPS[op].launch(b, kw), self.reduce)
+        return [_guarded(_OPS[op].outputs, b, r) for b, r in zip(bals, res)] if ok else [(ok, res)] * len(bals)
+
+
+class Distributed:
+    """One rank per process (one process per GPU) over torch.distributed: rank 0 announces
+    every call, and the ranks meet in the group's backend (RCCL over xGMI for ``nccl``)."""
+
+    def __init__(self):
+        import torch
+        import torch.distributed as dist
+        self.torch, self.dist, self.dev, self.ranks = torch, dist, _dev(dist), [dist.get_rank()]
+
+    def announce(self, op, kw):
+        _send_call(self.dist, self.dev, op, kw)
+
+    reduce = staticmethod(dist_reduce)
+
+    def phases(self, bals, op, kw):
+        return [rank_phases(b, op, kw) for b in bals]
+
+    def agree(self, flags, record):
+        """The held rank's guarded value to every rank: one fixed record per rank, all-gathered
+        -- (ok, code, the record's words) --, and only when a rank failed the messages, pickled.
+        ``record`` None: the guarded values pickled whole.  Returns, on every rank, the list of
+        (ok, value | (code, message)) in rank order."""
+        torch, dist, world, (ok, val) = self.torch, self.dist, self.dist.get_world_size(), flags[0]
+        if record is None:
+            outs = [None] * world
+            dist.all_gather_object(outs, flags[0])
+            return outs
+        rec = np.zeros(record.width, np.int64)
+        if ok:
+            words = record.pack(val)
+            rec[0], rec[2:2 + len(words)] = 1, words
         else:
-            z = np.zeros(0)
-            kw.update(ev_kind=z.astype(np.uint8), ev_slot=z.astype(np.int32), ev_val=z.astype(np.int32),
-                      ev_ts=z.astype(np.float64), ev_seq=z.astype(np.int64))
-    return op, kw
-
-
-def _gather_results(dist, dev, op, guarded):
-    """Every rank: its guarded result of a tick / purge.  Returns, on every rank, the
-    list of (ok, value | (code, message)) in rank order -- values complete on rank 0
-    (the other ranks get headers only, enough to settle the commit)."""
-    import torch
-    ok, val = guarded
-    rank, world = dist.get_rank(), dist.get_world_size()
-    h = torch.zeros(_HDR, dtype=torch.int64)
-    payload = np.zeros(0, np.uint8)
-    if ok:
-        r = val["result"]
-        # (rank 0 writes the whole assignment array itself, fb_set_full_assign: the other
-        # ranks send only their orphans and evicted slots, a few KB)
-        task = np.zeros(0, np.int64)
-        slot = np.zeros(0, np.int32)
-        orph = np.asarray(val["orphans"], np.int64)
-        evic = np.asarray(val["evicted"], np.int32)
-        h[0] = 1
-        h[2], h[3], h[4] = int(r.get("n_local", 0)), int(r.get("n_orphans_local", 0)), int(r["n_evicted"])
-        h[5], h[6], h[7] = len(task), len(orph), len(evic)
-        if rank != 0:
-            payload = np.concatenate([task.view(np.uint8), slot.view(np.uint8), orph.view(np.uint8),
-                                      evic.view(np.uint8)])
-    else:
-        h[1] = val[0] if val[0] is not None else 0
-    hs = [torch.zeros(_HDR, dtype=torch.int64, device=dev) for _ in range(world)]
-    dist.all_gather(hs, h.to(dev))
-    hs = [x.cpu().numpy() for x in hs]
-    if not all(x[0] for x in hs):
-        # a rank failed: its message (pickled: failures only)
+            rec[1] = val[0] if val[0] is not None else 0
+        recs = [torch.zeros(record.width, dtype=torch.int64, device=self.dev) for _ in range(world)]
+        dist.all_gather(recs, torch.from_numpy(rec).to(self.dev))
+        recs = [x.cpu().numpy() for x in recs]
         msgs = [None] * world
-        dist.all_gather_object(msgs, None if ok else val)
-        return [(bool(x[0]), None if x[0] else msgs[i]) for i, x in enumerate(hs)]
-    nbytes = [int(x[5]) * 12 + int(x[6]) * 8 + int(x[7]) * 4 for x in hs]
-    mx = max(nbytes[1:], default=0)
-    outs = [(True, val if rank == 0 else None)] + [(True, None)] * (world - 1)
-    if world > 1 and mx > 0:
-        mine = torch.zeros(mx, dtype=torch.uint8)
+        if not all(x[0] for x in recs):
+            dist.all_gather_object(msgs, None if ok else val)
+        return [(True, record.unpack(x[2:])) if x[0] else (False, msgs[i]) for i, x in enumerate(recs)]
+
+    def collect(self, vals, heads, lists):
+        """The ranks' lists to rank 0: one padded byte tensor per rank gathered there (none
+        when no other rank has bytes; ``heads``: what the ranks agreed on, which sizes them).
+        Returns, on rank 0, the ranks' values in rank order (its own as it is); else None."""
+        torch, dist, rank = self.torch, self.dist, self.ranks[0]
+        mx = max([lists.nbytes(h) for h in heads][1:], default=0)
+        bufs = None
+        if mx > 0:
+            mine = torch.zeros(mx, dtype=torch.uint8)
+            if rank != 0:
+                payload = lists.pack(vals[0])
+                mine[:len(payload)] = torch.from_numpy(payload)
+            bufs = [torch.zeros(mx, dtype=torch.uint8, device=self.dev) for _ in heads] if rank == 0 else None
+            dist.gather(mine.to(self.dev), bufs, dst=0)
         if rank != 0:
-            mine[:len(payload)] = torch.from_numpy(payload)
-        bufs = [torch.zeros(mx, dtype=torch.uint8, device=dev) for _ in range(world)] if rank == 0 else None
-        dist.gather(mine.to(dev), bufs, dst=0)
-        if rank == 0:
-            for i in range(1, world):
-                b = bufs[i].cpu().numpy()
-                nt, no, ne = int(hs[i][5]), int(hs[i][6]), int(hs[i][7])
-                o = [0, 8 * nt, 12 * nt, 12 * nt + 8 * no, 12 * nt + 8 * no + 4 * ne]
-                res = dict(n_local=int(hs[i][2]), n_orphans_local=int(hs[i][3]), n_evicted=int(hs[i][4]))
-                d = dict(result=res, orphans=b[o[2]:o[3]].view(np.int64).copy(),
-                         evicted=b[o[3]:o[4]].view(np.int32).copy(), reconnect=None)
-                outs[i] = (True, d)
-    elif rank == 0:
-        for i in range(1, world):
-            res = dict(n_local=int(hs[i][2]), n_orphans_local=int(hs[i][3]), n_evicted=int(hs[i][4]))
-            d = dict(result=res, orphans=np.zeros(0, np.int64), evicted=np.zeros(0, np.int32), reconnect=None)
-            outs[i] = (True, d)
-    return outs
-
-
-def _gather_stats(dist, dev, guarded):
-    """Every rank: its guarded part of a pool summary.  Returns, on every rank, the list of
-    (ok, (part, queue_len) | (code, message)) in rank order."""
-    import torch
-    ok, val = guarded
-    world = dist.get_world_size()
-    rec = np.zeros(_PS_REC, np.int64)
-    if ok:
-        rec = _pack_summary(*val)
-    else:
-        rec[1] = val[0] if val[0] is not None else 0
-    recs = [torch.zeros(_PS_REC, dtype=torch.int64, device=dev) for _ in range(world)]
-    dist.all_gather(recs, torch.from_numpy(rec).to(dev))
-    recs = [x.cpu().numpy() for x in recs]
-    if not all(x[0] for x in recs):
-        msgs = [None] * world
-        dist.all_gather_object(msgs, None if ok else val)
-        return [(bool(x[0]), None if x[0] else msgs[i]) for i, x in enumerate(recs)]
-    return [(True, _unpack_summary(x)) for x in recs]
-
-
-def _gather(dist, dev, op, guarded):
-    """The ranks' guarded results of one operation, on every rank, in rank order."""
-    if op in ("tick", "purge"):
-        return _gather_results(dist, dev, op, guarded)
-    if op == "stats":
-        return _gather_stats(dist, dev, guarded)
-    outs = [None] * dist.get_world_size()
-    dist.all_gather_object(outs, guarded)
-    return outs
+            return None
+        none = np.zeros(0, np.uint8)
+        return vals + [lists.unpack(heads[i], none if bufs is None else bufs[i].cpu().numpy()) for i in range(1, len(heads))]
 
 
 class DistShardGroup(ShardGroup):
     """Rank 0's view of a table sharded over a torch.distributed group (one process
     per GPU): every call is broadcast to the ranks (serve_shard() runs on the
     others), each rank runs it on its own shard -- ticks with the exchange
-    all-reduce over the group's backend (RCCL over xGMI for ``nccl``) -- and the
-    per-rank results come back to rank 0.  Ticks and purges travel as tensors (the
-    event batch in one broadcast, the results in one gather) and so do pool summaries (one
-    fixed record per rank), log compactions (the live bitmap all-reduced in place, a fixed
-    header per rank) and reclaims (a fixed header per rank, the lists in one gather); loads and
-    state reads as pickled objects."""
+    all-reduce over the group's backend -- and the per-rank results come back to rank 0."""
 
     def __init__(self, balancer, n_workers):
-        super().__init__(n_workers, (balancer,))
-        import torch.distributed as dist
-        self.dist, self.bal = dist, balancer
-        if dist.get_rank() != 0:
+        super().__init__(n_workers, [balancer], Distributed())
+        self.bal = balancer
+        if self.transport.ranks[0] != 0:
             raise FaasbalError(_lib.FB_ESTATE, "DistShardGroup lives on rank 0; run serve_shard() on the others")
-        self.dev = _dev(dist)
-        # rank 0's phase 2 writes the whole assignment array (the per-task gather is gone)
+        # rank 0's phase 2 writes the whole assignment array (no (task, slot) pairs travel)
         balancer.set_full_assign(True)
 
-    def _each(self, op, **kw):
-        _bcast_call(self.dist, self.dev, op, kw)
-        if op == "compact":
-            out, bad = _compact_rank(self.dist, self.dev, self.bal, kw)
-            if bad is not None:
-                _raise_bad(op, bad)
-            return [out]
-        if op == "reclaim":
-            parts, bad = _reclaim_rank(self.dist, self.dev, self.bal, kw)
-            if bad is not None:
-                _raise_bad(op, bad)
-            return parts
-        guarded = _serve_guarded(self.bal, op, kw)
-        outs = _gather(self.dist, self.dev, op, guarded)
-        bad = _settle(self.bal, op, outs)
-        if bad is not None:
-            _raise_bad(op, bad)
-        return [o[1] for o in outs]
-
     def close(self):
-        _bcast_call(self.dist, self.dev, "stop", {})
+        self.transport.announce("stop", {})
 
 
 def serve_shard(balancer):
     """Rank r > 0 of a DistShardGroup: run rank 0's calls on this shard until it stops."""
-    import torch.distributed as dist
-    dev = _dev(dist)
+    tp = Distributed()
     while True:
-        op, kw = _recv_call(dist, dev)
+        op, kw = _recv_call(tp.dist, tp.dev)
         if op == "stop":
             return
-        if op == "compact":
-            _compact_rank(dist, dev, balancer, kw)  # rank 0 raises a failure; this rank keeps serving
-            continue
-        if op == "reclaim":
-            _reclaim_rank(dist, dev, balancer, kw)  # (likewise: a refused reclaim changed nothing)
-            continue
-        guarded = _serve_guarded(balancer, op, kw)
-        outs = _gather(dist, dev, op, guarded)
-        _settle(balancer, op, outs)  # rank 0 raises a failure; this rank keeps serving
+        _OPS[op].run(tp, [balancer], op, kw)  # rank 0 raises a failure; this rank keeps serving
 
 
 class LocalShardGroup(ShardGroup):
-    """Every rank's shard in this process (one GPU, or rank contexts on several
-    devices); the exchange is summed on the device -- the reduction RCCL performs
-    across GPUs, byte for byte (one contributor per byte)."""
+    """Every rank's shard in this process (``.bals``), over the InProcess transport."""
 
     def __init__(self, world, n_workers, max_log, max_events=65536, device=0, rank_factory=None):
         make = rank_factory or (lambda r: ShardedBalancer(r, world, n_workers, max_log, max_events, device))
-        self.bals = [make(r) for r in range(world)]
-        super().__init__(n_workers, self.bals)
+        super().__init__(n_workers, [make(r) for r in range(world)], InProcess(world))
 
     def _each(self, op, **kw):
-        if op in ("tick", "purge"):
-            return self._collective(op, kw)
-        if op == "compact":
-            return self._compact(kw)
-        if op == "reclaim":
-            return self._reclaim(kw)
-        return [serve_op(b, op, kw) for b in self.bals]
-
-    def _reclaim(self, kw):
-        # every rank counts -- every refusal a rank would make, with nothing changed anywhere --
-        # and only when all of them can do the ranks take
-        counts = [_guarded(b.reclaim_part, kw["below_seq"], kw["slots"], True) for b in self.bals]
-        bad = next((c[1] for c in counts if not c[0]), None)
-        if bad is not None:
-            _raise_bad("reclaim", bad)
-        return [b.reclaim_part(kw["below_seq"], kw["slots"]) for b in self.bals]
-
-    def _compact(self, kw):
-        # mark on every rank, the bitmaps summed on the device (as _collective_once sums the
-        # exchange), apply on every rank -- or, when a rank could not mark or the total is not
-        # the caller's, cancel on every rank: nothing has changed anywhere
-        def guarded(f, *a):
-            try:
-                return (True, f(*a))
-            except Exception as e:  # noqa: BLE001 -- raised below, once every rank is cancelled
-                return (False, _failure(e))
-
-        total, bad = _compact_verdict([guarded(b.compact_mark) for b in self.bals], kw["expect"])
-        outs = []
-        if bad is None:
-            xs = [b.compact_exchange() for b in self.bals]
-            if xs[0].numel():
-                sync = self.bals[0].torch.cuda.synchronize if xs[0].is_cuda else (lambda: None)
-                sync()
-                union = xs[0].clone()
-                for x in xs[1:]:
-                    union += x
-                for x in xs:
-                    x.copy_(union)
-                sync()
-            outs = [guarded(b.compact_apply, total, bool(kw["want_kept"]) and r == 0) for r, b in enumerate(self.bals)]
-            bad = next((o[1] for o in outs if not o[0]), None)
-        if bad is not None:
-            for b in self.bals:
-                b.compact_cancel()
-            _raise_bad("compact", bad)
-        return [o[1] for o in outs]
-
-    def _collective(self, op, kw):
-        # phase 1 on every rank, then the summed exchange, then phase 2 / outputs / commit;
-        # relaunched with a wider round table while the ranks ask for it (FB_ERERUN)
-        for attempt in range(MAX_RELAUNCH + 1):
-            try:
-                return self._collective_once(op, kw)
-            except FaasbalError as e:
-                if e.code != FB_ERERUN or attempt == MAX_RELAUNCH:
-                    raise
+        return self._collective_once(op, kw) if _OPS[op].run is _tick else super()._each(op, **kw)
 
     def _collective_once(self, op, kw):
-        torch = self.bals[0].torch
-        for b in self.bals:
-            if op == "tick":
-                b.launch(kw["now"], kw["tte"], kw["ev_kind"], kw["ev_slot"], kw["ev_val"], kw["ev_ts"], kw["ev_seq"],
-                         kw["n_pending"])
-            else:
-                b._E = 0
-                b._chk(b.lib.fb_purge_launch(b.h, kw["now"], kw["tte"]))
-                n = C.c_int64()
-                b._chk(b.lib.fb_exchange_bytes(b.h, 0, C.byref(n)))
-                b._xbytes = n.value
-        torch.cuda.synchronize()
-        total = self.bals[0].exchange().clone()
-        for b in self.bals[1:]:
-            total += b.exchange()
-        for b in self.bals:
-            b.exchange().copy_(total)
-        torch.cuda.synchronize()
-        for b in self.bals:
-            b.cont()
-        res_all = []
-        err = None
-        for b in self.bals:  # every rank waits (a rerun request reaches them all)
-            try:
-                res_all.append(b.wait())
-            except FaasbalError as e:
-                err = err or e
-        if err is not None:
-            raise err
-        outs = []
-        for b, res in zip(self.bals, res_all):
-            if op == "tick":
-                task, slot = b.local_assignments()
-                outs.append(dict(result=res, task=task, slot=slot, orphans=b.orphans(), evicted=b.evicted(),
-                                 reconnect=b.event_status()))
-            else:
-                outs.append(dict(result=res, evicted=b.evicted(), orphans=b.orphans()))
-        for b in self.bals:
-            b.commit()
-        return outs
+        """A tick or purge on every rank, committed when all succeeded: the ranks' outputs, or
+        the failure raised.  The one seam besides the transport: a group of rank doubles that
+        cannot run the phases in step may put its own here (``serve_op`` per rank)."""
+        return super()._each(op, **kw)
 
     def close(self):
         for b in self.bals:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from faasbal import _lib
-from faasbal.sharded import LocalShardGroup, serve_op
+from faasbal.sharded import InProcess, LocalShardGroup, rank_phases
 from shard_model_balancer import ModelRankBalancer
 
 LC_TILE, LC_WORDS = 2048, 32  # kLcTile, kLcWords (csrc/faasbal_layout.h)
@@ -125,38 +125,37 @@ class CompactRank(ModelRankBalancer):
         return super().tick(*a, **k)
 
 
-class ModelGroup(LocalShardGroup):
-    """TEST DOUBLE: a LocalShardGroup whose ranks are model ranks.  A tick runs every rank's
-    model in a thread of its own, the exchange summed among them (one all-reduce per tick);
-    everything else is LocalShardGroup's."""
+class ThreadedRanks(InProcess):
+    """TEST DOUBLE's transport: in process, but a tick is every model rank's own tick() in a
+    thread of its own, the exchange summed among them at a barrier (one all-reduce per tick)."""
 
-    def __init__(self, world, n_workers, rank_cls=CompactRank):
-        super().__init__(world, n_workers, 0, rank_factory=lambda r: rank_cls(r, world, n_workers))
+    def phases(self, bals, op, kw):
+        bar, xs, outs, bad = threading.Barrier(len(bals)), [], [None] * len(bals), []
 
-    def _collective_once(self, op, kw):
-        n = len(self.bals)
-        bar, lock, acc = threading.Barrier(n), threading.Lock(), []
-
-        def allreduce(xt):
-            with lock:
-                acc.append(xt.clone())
+        def allreduce(x):
+            xs.append(x)
+            if bar.wait() == 0:
+                self.reduce(bals, xs)
             bar.wait()
-            xt.copy_(torch.stack(acc).sum(0, dtype=torch.uint8))
-
-        outs, errs = [None] * n, []
 
         def run(i, b):
-            try:
-                outs[i] = serve_op(b, op, kw, allreduce=allreduce)
-            except Exception as e:  # noqa: BLE001 -- raised below
-                errs.append(e)
+            outs[i] = rank_phases(b, op, kw, allreduce)
+            if not outs[i][0]:
+                bad.append(outs[i])  # (the first in time: the others' are the broken barrier)
                 bar.abort()
 
-        threads = [threading.Thread(target=run, args=(i, b)) for i, b in enumerate(self.bals)]
+        threads = [threading.Thread(target=run, args=(i, b)) for i, b in enumerate(bals)]
         for t in threads:
             t.start()
         for t in threads:
             t.join()
-        if errs:
-            raise errs[0]
-        return outs
+        return bad[:1] * len(bals) or outs
+
+
+class ModelGroup(LocalShardGroup):
+    """TEST DOUBLE: a LocalShardGroup whose ranks are model ranks, over ThreadedRanks;
+    everything else is LocalShardGroup's."""
+
+    def __init__(self, world, n_workers, rank_cls=CompactRank):
+        super().__init__(world, n_workers, 0, rank_factory=lambda r: rank_cls(r, world, n_workers))
+        self.transport = ThreadedRanks(world)
